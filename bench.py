@@ -5,11 +5,20 @@ online LDA k = 100, subsamplingRate 0.05 (≈50k docs per minibatch).  A "step" 
 OnlineLDAOptimizer.next(): device-side membership sampling, the E-step over the minibatch, the
 term-sorted sufficient statistics, the all-reduce (N > 1) and the λ / expElogβ / α update.  The
 corpus is resident in HBM before the timed region.  The headline computes in fp64 like Spark's
-Breeze Double E-step (--dtype f64); the fp32 path and the planted-topic (warm) model state are
-reported as secondary lines ("secondary") in the same JSON object at N = 1.
+Breeze Double E-step (--dtype f64).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f64|f32] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N   (one rank per GPU)
+
+A plain run does only what the headline needs: corpus, upload, the untimed minibatches to the fixed
+model state, the K timed steps, the result line (value, ms_per_step, and the roofline figures that
+come from the timed steps' own phase timers).  --full adds everything that takes runs of its own: the
+fp32 / mixed paths and the planted-topic (warm) model state as secondary lines ("secondary") in the
+same JSON object at N = 1, the featurisation line, the device-copy HBM probe and the CPU baseline
+(each still switched off by its --no-* option).  --dump-outputs DIR writes what the last timed step
+left its caller, the model (topicsMatrix λ, docConcentration α), as DIR/<name>.npy in float64; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Multi-GPU (configs[2]: "the same 1M-doc corpus sharded at 2/4/8 GPUs"): --scaling strong (default)
 gives rank r the rows [r·D/N, (r+1)·D/N) of ONE corpus (corpusSize = D); --scaling weak gives every
@@ -76,15 +85,23 @@ def parse():
     p.add_argument("--state-minibatches", type=int, default=20,
                    help="minibatches applied from λ₀ before timing (burn-in + warmup)")
     p.add_argument("--workers", type=int, default=16, help="corpus-generation processes (before GPU init)")
-    p.add_argument("--no-secondary", action="store_true", help="headline only (no fp32 / planted / featurisation)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also everything that takes runs of its own: the secondary lines (fp32 / mixed / planted / "
+                        "featurisation), the device-copy HBM probe and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the model the last timed step left (topics.npy, alpha.npy; float64) into DIR")
+    p.add_argument("--no-secondary", action="store_true",
+                   help="with --full: headline only (no fp32 / planted / featurisation)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     p.add_argument("--featurisation-only", action="store_true",
                    help="only the HashingTF -> IDF line (for profiling its kernels)")
-    p.add_argument("--no-hbm-copy", action="store_true", help="skip the device-copy HBM probe")
+    p.add_argument("--no-hbm-copy", action="store_true", help="with --full: skip the device-copy HBM probe")
     p.add_argument("--launch", default="auto", choices=["auto", "group"],
                    help="group: drive the GPUs through one stc_group even at N = 1 (with STC_GROUP_RCCL=1 "
                         "its RCCL communicator, ncclCommInitAll, and one host thread per member)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1 (the number of timed steps)")
     for key, v in PRESETS[a.config].items():
         if getattr(a, key) is None:
             setattr(a, key, v)
@@ -251,6 +268,22 @@ def cpu_baseline(h, corpus, a, budget_s=12.0):
                       f"E-step + per-thread dense k×V stats + reduce + λ/α update, fp64) from the GPU model "
                       f"after the timed steps; oracle/lda_oracle.c oracle_minibatch, OpenMP {threads} threads = {why}; "
                       f"mean inner iters {iters / max(1, done):.1f}; {dt:.1f} s"}
+
+
+DUMP_TOPICS_BYTES = 32 << 20  # --dump-outputs: the topicsMatrix rows kept (the whole dump stays far under 64 MB)
+
+
+def dump_outputs(path, h, seed):
+    """--dump-outputs: what a caller reads after the last timed next() — the topicsMatrix λ (V×k; past
+    DUMP_TOPICS_BYTES a fixed, seeded sample of its rows, in ascending row order) and docConcentration α,
+    as float64 DIR/topics.npy and DIR/alpha.npy."""
+    os.makedirs(path, exist_ok=True)
+    lam = h.topics()
+    keep = max(1, DUMP_TOPICS_BYTES // (8 * lam.shape[1]))
+    if lam.shape[0] > keep:
+        lam = lam[np.sort(np.random.default_rng(seed).choice(lam.shape[0], size=keep, replace=False))]
+    np.save(os.path.join(path, "topics.npy"), np.ascontiguousarray(lam, dtype=np.float64))
+    np.save(os.path.join(path, "alpha.npy"), np.ascontiguousarray(h.alpha(), dtype=np.float64))
 
 
 def featurization(stc, ctx, a, log, tokens, reps=5):
@@ -550,7 +583,8 @@ def main():
         corpus = synth.make_corpus(a.corpus, a.docs, a.tokens, a.vocab, a.k, seed, lo, hi, workers)
     gen_s = time.perf_counter() - t0
     log(f"{mode}: corpus rows [{lo}, {hi}) generated in {gen_s:.1f} s")
-    secondary = world == 1 and not a.no_secondary and mode != "group"  # (the secondary lines run on one context)
+    # (the secondary lines run on one context; like the HBM probe and the CPU baseline they belong to --full)
+    secondary = a.full and world == 1 and not a.no_secondary and mode != "group"
     planted = None
     if secondary:
         t0 = time.perf_counter()
@@ -629,6 +663,8 @@ def main():
     r = run_state(model, lam_head, barrier, log, a, a.dtype, a.steps, a.warmup)
     head = summarize(reduce_run(r), a, a.dtype, world, a.steps, a.corpus, kernel_name(r["kernels"]))
     h = model.h
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, h, a.seed + 3)
 
     lines = []
     if secondary:
@@ -659,9 +695,9 @@ def main():
         if dist is not None:
             dist.barrier()
         return
-    copy_gbs = None if a.no_hbm_copy else hbm_copy_gbs(local)
+    copy_gbs = hbm_copy_gbs(local) if a.full and not a.no_hbm_copy else None
     cpu = None
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         log("cpu baseline")
         cpu = cpu_baseline(h, corpus, a)
     roof = dict(head["roofline"], hbm_copy_measured_GBs=copy_gbs,

@@ -25,6 +25,9 @@ F3 ``en_topicdist.json`` — LocalLDAModel.topicDistribution known answers: the 
     independent runs: their spread is the fixture's noise floor).
 F4 metadata (α, η, k, gammaShape) from ``metadata/part-00000`` is copied into the json.
 F5 ``en_vocab.txt`` and F6 ``books_text.json`` — see make_vocab / make_text_samples.
+F7 ``LdaModel_EN_1591049082850/`` — the saved EN model's own files (make_model_copy).
+
+No fixture file is larger than 1 MiB: save_npz splits an .npz past that into parts.
 """
 import glob
 import json
@@ -37,6 +40,22 @@ import numpy as np
 REF = "/root/reference/TextClustering/src/main/resources"
 OUT = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(OUT))
+
+
+MAX_FILE = 1 << 20  # no committed file is larger than 1 MiB
+
+
+def save_npz(path, **arrays):
+    """np.savez_compressed, kept under MAX_FILE per file: while <path> is too large its largest array moves
+    into <stem>.<array>.npz beside it (tests/helpers.py golden_npz reads the parts back as one fixture)."""
+    arrays = dict(arrays)
+    np.savez_compressed(path, **arrays)
+    while os.path.getsize(path) > MAX_FILE and len(arrays) > 1:
+        key = max(arrays, key=lambda n: np.asarray(arrays[n]).nbytes)
+        part = f"{path[:-len('.npz')]}.{key}.npz"
+        np.savez_compressed(part, **{key: arrays.pop(key)})
+        assert os.path.getsize(part) <= MAX_FILE, part
+        np.savez_compressed(path, **arrays)
 
 
 def _read_table(d):
@@ -79,7 +98,7 @@ def make_idf(model, tag):
     assert np.array_equal(tf * idf_f[term], val), "recovered TF must reproduce the edges exactly"
     indptr = np.zeros(m + 1, np.int64)
     np.cumsum(np.bincount(doc, minlength=m), out=indptr[1:])
-    np.savez_compressed(
+    save_npz(
         os.path.join(OUT, f"{tag}_idf.npz"),
         indptr=indptr, indices=term.astype(np.int32), tf=tf, tfidf=val, doc_ids=doc_ids,
         num_docs=np.int64(m), vocab_size=np.int64(V), min_doc_freq=np.int64(2))
@@ -168,6 +187,24 @@ def make_en_model_fixtures(indptr, indices, tf, meta):
     print("describe/topicdist fixtures written")
 
 
+def make_model_copy():
+    """F7 ``LdaModel_EN_1591049082850/`` — the saved EM model itself, as Spark wrote it: its metadata line and
+    the parquet parts of data/{topicCounts,tokenCounts,globalTopicTotals} (no checksum side files), the input
+    of the DistributedLDAModel reader's test (tests/test_model_io.py)."""
+    import shutil
+
+    model = "LdaModel_EN_1591049082850"
+    src = os.path.join(REF, "models", model)
+    files = [os.path.join("metadata", "part-00000")]
+    for d in ("topicCounts", "tokenCounts", "globalTopicTotals"):
+        files += [os.path.relpath(f, src) for f in sorted(glob.glob(os.path.join(src, "data", d, "*.parquet")))]
+    for f in files:
+        assert os.path.getsize(os.path.join(src, f)) <= MAX_FILE, f
+        os.makedirs(os.path.dirname(os.path.join(OUT, model, f)), exist_ok=True)
+        shutil.copyfile(os.path.join(src, f), os.path.join(OUT, model, f))
+    print(f"{model}: {len(files)} files copied")
+
+
 def make_vocab():
     """F5 ``en_vocab.txt`` — the EN model's vocabulary (vocabArray, index = term id, one per line), the
     strings behind en_idf.npz's term ids: the config-1 pipeline test hashes them (HashingTF)."""
@@ -247,5 +284,6 @@ if __name__ == "__main__":
     ip, ix, tf, meta = make_idf("LdaModel_EN_1591049082850", "en")
     make_idf("LdaModel_GE_1591070442475", "ge")
     make_en_model_fixtures(ip, ix, tf, meta)
+    make_model_copy()
     make_vocab()
     make_text_samples()

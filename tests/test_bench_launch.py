@@ -60,6 +60,12 @@ class FakeGroup:
     def transport(self):
         return "rccl" if len(self.devices) > 1 else "none"
 
+    def topics(self):  # a model that records how many steps made it
+        return np.arange(self.V * self.k, dtype=np.float64).reshape(self.V, self.k) + self.steps
+
+    def alpha(self):
+        return np.full(self.k, 0.5 + self.steps)
+
     def counters(self):
         n = len(self.devices)
         return [{"docs": 10 * self.steps, "entries": 1000 * self.steps, "inner_iters": 50 * self.steps,
@@ -125,6 +131,51 @@ def test_group_launch_at_one_gpu(monkeypatch, capsys):
                                             "--no-hbm-copy", "--no-cpu-baseline"], n_dev=1)
     (g,) = FakeGroup.made
     assert g.devices == [0] and line["n_gpus"] == 1 and line["config"]["parallelism"] == "group1"
+
+
+SMALL = ["--launch", "group", "--steps", "2", "--warmup", "0", "--docs", "800", "--tokens", "10", "--vocab", "1024",
+         "--k", "4", "--workers", "1"]
+
+
+def test_plain_run_is_headline_only_and_full_adds_the_rest(monkeypatch, capsys):
+    """Without --full nothing beside the headline runs (no HBM copy probe, no CPU baseline, no secondary
+    lines); --full runs them, each still switched off by its --no-* option."""
+    calls = []
+    monkeypatch.setattr(bench, "hbm_copy_gbs", lambda dev: calls.append("copy") or 5000.0)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda h, corpus, a: calls.append("cpu") or {"value": 1.0})
+    line = _run_bench(monkeypatch, capsys, SMALL, n_dev=1)
+    assert calls == []
+    assert line["cpu_baseline"] is None and line["secondary"] == [] and line["roofline"]["hbm_copy_measured_GBs"] is None
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "docs/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["metric"] == bench.METRIC
+    assert FakeGroup.made[0].steps == 20 + 2  # the fixed model state (20 minibatches), then exactly --steps
+    line = _run_bench(monkeypatch, capsys, SMALL + ["--full"], n_dev=1)
+    assert calls == ["copy", "cpu"]
+    assert line["cpu_baseline"] == {"value": 1.0} and line["roofline"]["hbm_copy_measured_GBs"] == 5000.0
+    calls.clear()
+    _run_bench(monkeypatch, capsys, SMALL + ["--full", "--no-hbm-copy", "--no-cpu-baseline"], n_dev=1)
+    assert calls == []
+
+
+def test_dump_outputs_writes_the_model_after_the_last_timed_step(monkeypatch, capsys, tmp_path):
+    """--dump-outputs DIR: topics.npy (V×k) and alpha.npy (k) in float64, read after the last timed step;
+    a topicsMatrix past the byte cap is a fixed, seeded sample of its rows (the same rows in every run)."""
+    d = tmp_path / "out"
+    _run_bench(monkeypatch, capsys, SMALL + ["--dump-outputs", str(d)], n_dev=1)
+    lam, alpha = np.load(d / "topics.npy"), np.load(d / "alpha.npy")
+    assert sorted(os.listdir(d)) == ["alpha.npy", "topics.npy"]
+    assert lam.dtype == np.float64 and alpha.dtype == np.float64
+    assert np.array_equal(lam, FakeGroup.made[0].topics()) and lam[0, 0] == 22.0
+    assert np.array_equal(alpha, np.full(4, 22.5))
+    monkeypatch.setattr(bench, "DUMP_TOPICS_BYTES", 100 * 4 * 8)  # room for 100 of the 1024 rows
+    d2, d3 = tmp_path / "s1", tmp_path / "s2"
+    _run_bench(monkeypatch, capsys, SMALL + ["--dump-outputs", str(d2)], n_dev=1)
+    _run_bench(monkeypatch, capsys, SMALL + ["--dump-outputs", str(d3)], n_dev=1)
+    s = np.load(d2 / "topics.npy")
+    assert s.shape == (100, 4) and np.array_equal(s, np.load(d3 / "topics.npy"))
+    rows = ((s[:, 0] - 22.0) / 4).astype(int)  # FakeGroup.topics: row r starts at 4r + steps
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s, lam[rows])
 
 
 def test_gpus_n_fails_loudly_when_fewer_devices_are_visible(monkeypatch, capsys):

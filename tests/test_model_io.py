@@ -1,16 +1,16 @@
 """Model persistence (stc.io): LocalLDAModel / DistributedLDAModel in Spark
-mllib's SaveLoadV1_0 layout.  CPU tests (pyarrow only).  The reference's own saved EM model is read
-when /root/reference is present (this container, never the GPU box) and checked against the
-committed fixtures that tests/golden/make_golden.py extracted from the same files."""
+mllib's SaveLoadV1_0 layout.  CPU tests (pyarrow only).  The reference's own saved EM model (the
+copy of its files under tests/golden/, fixture F7) is read and checked against the committed
+fixtures that tests/golden/make_golden.py extracted from the same files."""
 import json
 import os
 
 import numpy as np
 import pytest
 
-from helpers import golden_npz
+from helpers import GOLDEN, golden_npz
 
-REF_MODEL = "/root/reference/TextClustering/src/main/resources/models/LdaModel_EN_1591049082850"
+REF_MODEL = os.path.join(GOLDEN, "LdaModel_EN_1591049082850")
 
 
 def _io():
@@ -95,7 +95,6 @@ def test_distributed_model_round_trip(tmp_path):
     assert np.array_equal(m["iteration_times"], [0.5, 0.25])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODEL), reason="reference not present (GPU box)")
 def test_reads_the_reference_saved_em_model():
     """LDALoader.scala:37's DistributedLDAModel.load of the reference's own EN model: its term
     vertices equal the committed n_wk fixture, its edges the committed TF·IDF values (F1/F2)."""

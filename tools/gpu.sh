@@ -5,7 +5,7 @@
 #
 # Recipes (run in the order given):
 #   check              pytest -m gpu (PYTEST_K / TESTS narrow it) + smoke
-#   bench              the default bench line (python bench.py) → gpurun_out/bench.json
+#   bench              the full bench line (python bench.py --full) → bench.json beside the logs
 #   ab                 headline + planted lines of the in-tree library and of each LIBS variant
 #                      (libstc_<n>.so); DTYPE=f32 for the fp32 kernels
 #   configs            BASELINE configs 4 / 5 lines, fp64 + fp32, with the CPU baseline (DTYPES narrows)
@@ -41,7 +41,7 @@ r_check() {
   step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
 }
 r_bench() {
-  step bench ${BENCH_SECS:-600} python bench.py ${BENCH_ARGS:-}
+  step bench ${BENCH_SECS:-600} python bench.py --full ${BENCH_ARGS:-}
   tail -n 1 gpurun_out/bench.log > gpurun_out/bench.json
 }
 r_ab() {
@@ -54,7 +54,7 @@ r_ab() {
   done
 }
 r_configs() {
-  local B="python bench.py --steps 20 --warmup 10 --no-secondary --no-hbm-copy"
+  local B="python bench.py --full --steps 20 --warmup 10 --no-secondary --no-hbm-copy"
   for c in 4 5; do
     for dt in ${DTYPES:-f64 f32}; do
       step c${c}_$dt 700 $B --config $c --dtype $dt $( [ "$dt" = f32 ] && echo --no-cpu-baseline )
