@@ -24,6 +24,9 @@
  *                               LDALoader.scala:66
  *   stc_lda_topic_distribution  toLocal.topicDistribution(tf) — LDALoader.scala:108
  *   stc_lda_bound               [U] LocalLDAModel.logLikelihood / logPerplexity
+ *   stc_em_*                    [U] EMLDAOptimizer, the reference's default optimizer ("em", Params.scala:9) —
+ *                               LDAClustering.scala:41; stc_em_log_likelihood is
+ *                               DistributedLDAModel.logLikelihood / logPrior — LDAClustering.scala:75
  *   stc_comm_*                  the role of Spark's broadcast + treeReduce inside lda.run
  *                               (per minibatch: RCCL reduce-scatter of the k×V sstats over
  *                               vocabulary slices, the slice's λ update, all-gather of expElogβ)
@@ -301,6 +304,43 @@ enum stc_kernel_count {
   STC_KC_N = 12
 };
 int stc_lda_kernel_counts(stc_lda* lda, int64_t out[12]);
+
+/* ---- EM LDA ([U] EMLDAOptimizer → DistributedLDAModel) ------------------------------------
+ * The corpus is a bipartite graph: every CSR entry (document d, term w, value c != 0) is an edge; entries
+ * whose value is exactly 0 are not edges, and a document or term without an edge has no vertex (its row of
+ * the state is 0).  State, fp64: doc_topics N_dk (D×k), term_topics N_wk (V×k, the model's unnormalised
+ * topicsMatrix), totals N_k = Σ_w N_wk.  One iteration: along every edge the message c·γ with
+ *   γ_j ∝ (N_wk[w][j] + η−1)(N_dk[d][j] + α−1) / (N_k[j] + V(η−1)),  Σ_j γ_j = 1,
+ * all reads from the old state; a vertex's new counts are the sum of the messages of its edges.
+ * α (symmetric) and η: −1 picks Spark's EM defaults 50/k + 1 and 1.1; anything else must be > 1.
+ * 2 <= k <= 1024.  The results are bitwise reproducible (no float atomics; fixed summation orders).
+ * Single device: every call on a context connected to other ranks returns STC_ERR_STATE.       */
+typedef struct stc_em stc_em;
+/* builds the graph on the device (the filtered CSR and its transpose) from an STC_F64 `corpus` of ctx (an
+ * STC_F32 one: STC_ERR_INVALID_ARG).  The handle copies what it needs and keeps no reference to `corpus`. */
+int stc_em_create(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
+                  double topic_concentration, stc_em** out);
+/* waits for queued iterations, then frees the device memory (valid after stc_destroy of the context) */
+int stc_em_destroy(stc_em* em);
+/* any may be NULL; n_edges counts the non-zero entries */
+int stc_em_shape(const stc_em* em, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges);
+/* every edge draws k uniforms in (0,1) from the counter RNG keyed (seed, the edge's position among the
+ * edges in CSR order, topic) and normalises them to sum 1: N_dk[d] += c·γ_e, N_wk[w] += c·γ_e */
+int stc_em_init_random(stc_em* em, uint64_t seed);
+/* state injection: doc_topics D×k, term_topics V×k (non-negative); rows of documents / terms without an
+ * edge are stored as 0, N_k is derived */
+int stc_em_set_state(stc_em* em, const double* doc_topics, const double* term_topics);
+/* doc_topics D×k, term_topics V×k, totals k, the resolved α and η; any may be NULL.  Waits for queued
+ * iterations.  The three arrays need a state (STC_ERR_STATE before init_random / set_state). */
+int stc_em_get_state(stc_em* em, double* doc_topics, double* term_topics, double* totals, double* alpha_out,
+                     double* eta_out);
+/* n_iterations × EMLDAOptimizer.next(); enqueues on the context's stream and does not wait
+ * (stc_synchronize, or any call that copies results out, does).  STC_ERR_STATE without a state. */
+int stc_em_next(stc_em* em, int32_t n_iterations);
+/* DistributedLDAModel.logLikelihood = Σ_edges c·ln(φ_w · θ_d), φ_w[j] = (N_wk[w][j] + η−1) / (N_k[j] + V(η−1)),
+ * θ_d = (N_dk[d] + α−1) normalised; logPrior = (η−1) Σ_terms Σ_j ln φ_w[j] + (α−1) Σ_docs Σ_j ln θ_d[j] over
+ * the vertices that exist.  Either may be NULL.  STC_ERR_STATE without a state. */
+int stc_em_log_likelihood(stc_em* em, double* log_likelihood_out, double* log_prior_out);
 
 /* ---- one process, N devices ---------------------------------------------------------------
  * The reference trains in ONE JVM (Spark local[*], LDATraining.scala:7), so its drop-in drives every GPU

@@ -32,6 +32,7 @@
 #define CSR(h) ((stc_dcsr*)(intptr_t)(h))
 #define LDA(h) ((stc_lda*)(intptr_t)(h))
 #define GRP(h) ((stc_group*)(intptr_t)(h))
+#define EM(h) ((stc_em*)(intptr_t)(h))
 
 static int check(JNIEnv* env, int st) {
   if (st == STC_OK) return 0;
@@ -604,6 +605,81 @@ JNIEXPORT jlong JNICALL FN(ldaPhaseTimes)(JNIEnv* env, jclass c, jlong lda, jdou
   UNPIN(Double, ms_out, p, 0);
   check(env, st);
   return steps;
+}
+
+/* ---- EM LDA (stc_em: EMLDAOptimizer / DistributedLDAModel) ---------------------------------------- */
+static int em_shape(JNIEnv* env, jlong em, int64_t s[4]) {
+  int32_t k = 0;
+  if (check(env, stc_em_shape(EM(em), &k, &s[1], &s[2], &s[3]))) return 1;
+  s[0] = k;
+  return 0;
+}
+
+JNIEXPORT jlong JNICALL FN(emCreate)(JNIEnv* env, jclass c, jlong ctx, jlong dcsr, jint k, jdouble alpha, jdouble eta) {
+  stc_em* out = NULL;
+  if (check(env, stc_em_create(CTX(ctx), CSR(dcsr), k, alpha, eta, &out))) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT void JNICALL FN(emDestroy)(JNIEnv* env, jclass c, jlong em) { check(env, stc_em_destroy(EM(em))); }
+
+/* {k, nDocs, vocabSize, nEdges} */
+JNIEXPORT jlongArray JNICALL FN(emShape)(JNIEnv* env, jclass c, jlong em) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (em_shape(env, em, s)) return NULL;
+  jlongArray out = (*env)->NewLongArray(env, 4);
+  if (out) (*env)->SetLongArrayRegion(env, out, 0, 4, (const jlong*)s);
+  return out;
+}
+
+JNIEXPORT void JNICALL FN(emInitRandom)(JNIEnv* env, jclass c, jlong em, jlong seed) {
+  check(env, stc_em_init_random(EM(em), (uint64_t)seed));
+}
+
+JNIEXPORT void JNICALL FN(emSetState)(JNIEnv* env, jclass c, jlong em, jdoubleArray doc_topics,
+                                      jdoubleArray term_topics) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (em_shape(env, em, s) || NEED(doc_topics, s[1] * s[0], "emSetState docTopics") ||
+      NEED(term_topics, s[2] * s[0], "emSetState termTopics"))
+    return;
+  jdouble* d = PIN(jdouble, Double, doc_topics);
+  jdouble* t = PIN(jdouble, Double, term_topics);
+  int st = stc_em_set_state(EM(em), d, t);
+  UNPIN(Double, term_topics, t, JNI_ABORT);
+  UNPIN(Double, doc_topics, d, JNI_ABORT);
+  check(env, st);
+}
+
+/* every array nullable; alphaEta (2) receives the resolved docConcentration and topicConcentration */
+JNIEXPORT void JNICALL FN(emGetState)(JNIEnv* env, jclass c, jlong em, jdoubleArray doc_topics,
+                                      jdoubleArray term_topics, jdoubleArray totals, jdoubleArray alpha_eta) {
+  int64_t s[4] = {0, 0, 0, 0};
+  double ae[2] = {0, 0};
+  if (em_shape(env, em, s) || NEED(doc_topics, s[1] * s[0], "emGetState docTopics") ||
+      NEED(term_topics, s[2] * s[0], "emGetState termTopics") || NEED(totals, s[0], "emGetState totals") ||
+      NEED(alpha_eta, 2, "emGetState alphaEta"))
+    return;
+  jdouble* d = PIN(jdouble, Double, doc_topics);
+  jdouble* t = PIN(jdouble, Double, term_topics);
+  jdouble* n = PIN(jdouble, Double, totals);
+  int st = stc_em_get_state(EM(em), d, t, n, &ae[0], &ae[1]);
+  UNPIN(Double, totals, n, 0);
+  UNPIN(Double, term_topics, t, 0);
+  UNPIN(Double, doc_topics, d, 0);
+  if (!check(env, st) && alpha_eta) (*env)->SetDoubleArrayRegion(env, alpha_eta, 0, 2, ae);
+}
+
+JNIEXPORT void JNICALL FN(emNext)(JNIEnv* env, jclass c, jlong em, jint n_iterations) {
+  check(env, stc_em_next(EM(em), n_iterations));
+}
+
+/* {logLikelihood, logPrior} */
+JNIEXPORT jdoubleArray JNICALL FN(emLogLikelihood)(JNIEnv* env, jclass c, jlong em) {
+  double r[2] = {0, 0};
+  if (check(env, stc_em_log_likelihood(EM(em), &r[0], &r[1]))) return NULL;
+  jdoubleArray out = (*env)->NewDoubleArray(env, 2);
+  if (out) (*env)->SetDoubleArrayRegion(env, out, 0, 2, r);
+  return out;
 }
 
 /* ---- one process, N devices (stc_group) ---------------------------------------------------------- */

@@ -106,6 +106,22 @@ public final class StcNative {
   /** E-step launches per kernel family (stc.h enum stc_kernel_count), 12 words */
   public static native void ldaKernelCounts(long lda, long[] out12);
 
+  // ---- EM LDA (stc_em_*: EMLDAOptimizer / DistributedLDAModel; docConcentration / topicConcentration −1 = auto)
+  public static native long emCreate(long ctx, long dcsr, int k, double docConcentration, double topicConcentration);
+  public static native void emDestroy(long em);
+  /** {k, nDocs, vocabSize, nEdges} of the handle */
+  public static native long[] emShape(long em);
+  public static native void emInitRandom(long em, long seed);
+  /** docTopics nDocs×k, termTopics vocabSize×k (row-major) */
+  public static native void emSetState(long em, double[] docTopics, double[] termTopics);
+  /** every array nullable: docTopics nDocs×k, termTopics vocabSize×k, totals k, alphaEta 2 */
+  public static native void emGetState(long em, double[] docTopics, double[] termTopics, double[] totals,
+                                       double[] alphaEta);
+  /** enqueues nIterations EM iterations (does not wait) */
+  public static native void emNext(long em, int nIterations);
+  /** {logLikelihood, logPrior} */
+  public static native double[] emLogLikelihood(long em);
+
   // ---- host helpers (pure Java): Spark vectors → CSR arrays
   /** CSR of sparse or dense rows: {indptr long[n+1], indices int[nnz], values double[nnz]} */
   public static Object[] toCsr(org.apache.spark.mllib.linalg.Vector[] rows) {

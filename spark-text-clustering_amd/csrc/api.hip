@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <unordered_set>
 
+#include "lda_em.h"
 #include "lda_kernels.h"
 
 namespace stc {
@@ -2516,6 +2517,63 @@ int stc_lda_counters(stc_lda* L, int64_t out[4]) {
     out[1] = L->cum_entries;
     out[2] = c2[0];
     out[3] = c2[1];
+  });
+}
+
+// ---- EM LDA (lda_em.hip) -------------------------------------------------------------------
+int stc_em_create(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
+                  double topic_concentration, stc_em** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && corpus && out, "ctx/corpus/out");
+    STC_REQUIRE(corpus->ctx == ctx, "the corpus belongs to another stc_ctx");
+    *out = em::create(*ctx, *corpus, k, doc_concentration, topic_concentration);
+  });
+}
+
+int stc_em_destroy(stc_em* m) {
+  return guard([&] { em::destroy(m); });
+}
+
+int stc_em_shape(const stc_em* m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::shape(*m, k, n_docs, vocab, n_edges);
+  });
+}
+
+int stc_em_init_random(stc_em* m, uint64_t seed) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::init_random(*m, seed);
+  });
+}
+
+int stc_em_set_state(stc_em* m, const double* doc_topics, const double* term_topics) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::set_state(*m, doc_topics, term_topics);
+  });
+}
+
+int stc_em_get_state(stc_em* m, double* doc_topics, double* term_topics, double* totals, double* alpha_out,
+                     double* eta_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::get_state(*m, doc_topics, term_topics, totals, alpha_out, eta_out);
+  });
+}
+
+int stc_em_next(stc_em* m, int32_t n_iterations) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::next(*m, n_iterations);
+  });
+}
+
+int stc_em_log_likelihood(stc_em* m, double* log_likelihood_out, double* log_prior_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::log_likelihood(*m, log_likelihood_out, log_prior_out);
   });
 }
 

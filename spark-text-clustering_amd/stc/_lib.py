@@ -125,6 +125,14 @@ SIGNATURES = {
     "stc_lda_phase_times": (_int, [_p, _pdbl, _pi64]),
     "stc_lda_counters": (_int, [_p, _pi64]),
     "stc_lda_kernel_counts": (_int, [_p, _pi64]),
+    "stc_em_create": (_int, [_p, _p, _i32, _dbl, _dbl, C.POINTER(_p)]),
+    "stc_em_destroy": (_int, [_p]),
+    "stc_em_shape": (_int, [_p, _pi32, _pi64, _pi64, _pi64]),
+    "stc_em_init_random": (_int, [_p, _u64]),
+    "stc_em_set_state": (_int, [_p, _pdbl, _pdbl]),
+    "stc_em_get_state": (_int, [_p, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
+    "stc_em_next": (_int, [_p, _i32]),
+    "stc_em_log_likelihood": (_int, [_p, _pdbl, _pdbl]),
     "stc_group_create": (_int, [_pi32, _int, C.POINTER(LdaConfig), C.POINTER(_p)]),
     "stc_group_destroy": (_int, [_p]),
     "stc_group_size": (_int, [_p, _pi32]),

@@ -1,4 +1,4 @@
-"""Online-variational-Bayes LDA with the Spark ML / mllib surface, backed by libstc (K6–K12).
+"""LDA with the Spark ML / mllib surface, backed by libstc: online variational Bayes (K6–K12) and EM.
 
 * ``LDA`` / ``LDAModel`` mirror ``org.apache.spark.ml.clustering.{LDA, LocalLDAModel}``
   ([U] spark 2.4.3): k=10, maxIter=20, optimizer="online", learningOffset=1024,
@@ -8,8 +8,13 @@
   LDAClustering.scala:37-61 (``new LDA().setOptimizer(new OnlineLDAOptimizer()
   .setMiniBatchFraction(0.05 + 1.0 / N)).setK(..).setMaxIterations(..)...run(corpus)``).
 
-Only the online optimizer exists here; ``"em"`` (the reference's default, Params.scala:9) is out of
-scope and raises like an unknown optimizer does in LDAClustering.scala:44-45.
+* ``EMLDAOptimizer`` + ``MllibLDA.setOptimizer("em")`` is the reference's default branch (Params.scala:9,
+  LDAClustering.scala:40-41): ``run`` trains on the GPU through an ``EmHandle`` (stc_em_*: the corpus as a
+  bipartite graph, N_dk / N_wk / N_k in fp64) and returns a ``DistributedLDAModel`` with logLikelihood,
+  logPrior, topicDistributions, topTopicsPerDocument, topDocumentsPerTopic and save.
+
+The ml estimator ``LDA`` stays online-only (the reference selects EM on the mllib class); an optimizer
+other than "em" / "online" raises as in LDAClustering.scala:44-45.
 """
 from __future__ import annotations
 
@@ -353,6 +358,69 @@ class LdaGroup:
         self.close()
 
 
+class EmHandle:
+    """Owns one stc_em: the EM optimizer's bipartite graph (built once from ``corpus``, which may be freed
+    afterwards) and its state N_dk (D×k), N_wk (V×k), N_k on the GPU.  ``doc_concentration`` /
+    ``topic_concentration``: −1 picks Spark's EM defaults 50/k + 1 and 1.1, anything else must be > 1."""
+
+    def __init__(self, ctx: Context, corpus: DeviceCsr, k, doc_concentration=-1.0, topic_concentration=-1.0):
+        self.ctx = ctx
+        self.handle = None
+        h = C.c_void_p()
+        L.check(ctx.lib.stc_em_create(ctx.handle, corpus.handle, int(k), float(doc_concentration),
+                                      float(topic_concentration), C.byref(h)))
+        self.handle = h
+        kk, d, v, e = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(ctx.lib.stc_em_shape(h, C.byref(kk), C.byref(d), C.byref(v), C.byref(e)))
+        self.k, self.num_docs, self.vocab_size, self.num_edges = kk.value, d.value, v.value, e.value
+
+    def init_random(self, seed):
+        L.check(self.ctx.lib.stc_em_init_random(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_state(self, doc_topics, term_topics):
+        dt, tt = L.as_f64(doc_topics), L.as_f64(term_topics)
+        if dt.shape != (self.num_docs, self.k) or tt.shape != (self.vocab_size, self.k):
+            raise ValueError(f"state shapes {dt.shape}, {tt.shape}: expected ({self.num_docs}, {self.k}) and "
+                             f"({self.vocab_size}, {self.k})")
+        L.check(self.ctx.lib.stc_em_set_state(self.handle, L.ptr(dt, C.c_double), L.ptr(tt, C.c_double)))
+
+    def state(self):
+        """(N_dk D×k, N_wk V×k, N_k k); waits for queued iterations"""
+        dt = np.zeros((self.num_docs, self.k), np.float64)
+        tt = np.zeros((self.vocab_size, self.k), np.float64)
+        nk = np.zeros(self.k, np.float64)
+        L.check(self.ctx.lib.stc_em_get_state(self.handle, L.ptr(dt, C.c_double), L.ptr(tt, C.c_double),
+                                              L.ptr(nk, C.c_double), None, None))
+        return dt, tt, nk
+
+    def concentrations(self):
+        """the resolved (docConcentration α, topicConcentration η)"""
+        a, e = C.c_double(), C.c_double()
+        L.check(self.ctx.lib.stc_em_get_state(self.handle, None, None, None, C.byref(a), C.byref(e)))
+        return a.value, e.value
+
+    def next(self, n_iterations=1):
+        """enqueues n EM iterations (does not wait for the GPU)"""
+        L.check(self.ctx.lib.stc_em_next(self.handle, int(n_iterations)))
+
+    def log_likelihood(self):
+        """(logLikelihood, logPrior) of the current state"""
+        ll, lp = C.c_double(), C.c_double()
+        L.check(self.ctx.lib.stc_em_log_likelihood(self.handle, C.byref(ll), C.byref(lp)))
+        return ll.value, lp.value
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.stc_em_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _as_device(ctx, data, dtype):
     if isinstance(data, DeviceCsr):
         return data, False
@@ -447,9 +515,14 @@ class DistributedLDAModel:
     """[U] DistributedLDAModel as the reference loads it (LDALoader.scala:37): the saved EM graph, read
     from its parquet layout (stc.io).  What the reference then asks of it — describeTopics
     (LDALoader.scala:66) and toLocal.topicDistribution (:108) — runs on the GPU through ``toLocal``
-    (topicsMatrix = the term vertices' counts n_wk)."""
+    (topicsMatrix = the term vertices' counts n_wk).
 
-    def __init__(self, data):
+    It is also what ``MllibLDA.run`` returns under the EM optimizer (LDAClustering.scala:41, :61-63): the
+    trained graph's state read back from its ``EmHandle``.  ``logLikelihood`` / ``logPrior``
+    (LDAClustering.scala:75) run on the GPU; a loaded model builds its ``EmHandle`` from the stored edges
+    and state on first use, so the reference's own saved models can be scored."""
+
+    def __init__(self, data, em: "EmHandle | None" = None):
         self._d = data
         self.k, self.vocabSize = data["k"], data["vocab_size"]
         self.docConcentration = data["alpha"]
@@ -457,6 +530,83 @@ class DistributedLDAModel:
         self.gammaShape = data["gamma_shape"]
         self.iterationTimes = data["iteration_times"]
         self._local = {}
+        self._em = em
+
+    @staticmethod
+    def _from_em(em: "EmHandle", corpus: CsrMatrix, iteration_times, gamma_shape=100.0) -> "DistributedLDAModel":
+        """the model of a trained EmHandle over the host copy of its corpus (vertex id = row index)"""
+        ndk, nwk, nk = em.state()
+        alpha, eta = em.concentrations()
+        keep = corpus.values != 0.0
+        src = np.repeat(np.arange(corpus.num_rows, dtype=np.int64), np.diff(corpus.indptr))[keep]
+        doc_ids = np.unique(src)
+        return DistributedLDAModel({
+            "topics": nwk, "global_topic_totals": nk, "doc_ids": doc_ids, "doc_topics": ndk[doc_ids],
+            "edges": (src, corpus.indices[keep].astype(np.int64), corpus.values[keep]),
+            "alpha": np.full(em.k, alpha), "eta": eta, "gamma_shape": float(gamma_shape),
+            "iteration_times": np.asarray(iteration_times, np.float64), "k": em.k, "vocab_size": em.vocab_size}, em=em)
+
+    def _em_handle(self, ctx: Context | None = None) -> "EmHandle":
+        """the GPU graph of this model: the trainer's, or one built from the stored edges and state"""
+        if self._em is None:
+            d = self._d
+            alpha = np.asarray(d["alpha"], np.float64)
+            if np.any(alpha != alpha[0]):
+                raise ValueError("an EM model has a symmetric docConcentration")
+            src, term, cnt = d["edges"]
+            row = np.searchsorted(d["doc_ids"], src)
+            if row.size and (row.max() >= d["doc_ids"].size or np.any(d["doc_ids"][row] != src)):
+                raise ValueError("an edge names a document that has no vertex")
+            order = np.argsort(row, kind="stable")
+            indptr = np.zeros(d["doc_ids"].size + 1, np.int64)
+            np.cumsum(np.bincount(row, minlength=d["doc_ids"].size), out=indptr[1:])
+            ctx = ctx or Context.get()
+            dev = DeviceCsr.upload(ctx, CsrMatrix(indptr, term[order], cnt[order], self.vocabSize), L.STC_F64)
+            try:
+                em = EmHandle(ctx, dev, self.k, float(alpha[0]), float(d["eta"]))
+            finally:
+                dev.free()
+            em.set_state(d["doc_topics"], d["topics"])
+            self._em = em
+        return self._em
+
+    def logLikelihood(self, ctx: Context | None = None):
+        """[U] DistributedLDAModel.logLikelihood: Σ_edges c · ln(φ_w · θ_d) of the training corpus"""
+        return self._em_handle(ctx).log_likelihood()[0]
+
+    def logPrior(self, ctx: Context | None = None):
+        """[U] DistributedLDAModel.logPrior: ln P(topics, topic distributions | α, η) up to its constant"""
+        return self._em_handle(ctx).log_likelihood()[1]
+
+    def topicDistributions(self):
+        """(document ids, D'×k matrix): N_dk[d] / Σ_j N_dk[d][j] for every document vertex"""
+        dt = self._d["doc_topics"]
+        return self._d["doc_ids"].copy(), dt / dt.sum(axis=1, keepdims=True)
+
+    def topTopicsPerDocument(self, k):
+        """[(document id, topic indices, topic weights)], each document's top k topics by weight descending"""
+        ids, td = self.topicDistributions()
+        n = min(int(k), self.k)
+        top = np.argsort(-td, axis=1, kind="stable")[:, :n]
+        return [(int(ids[i]), top[i], td[i, top[i]]) for i in range(ids.size)]
+
+    def topDocumentsPerTopic(self, maxDocumentsPerTopic):
+        """[(document ids, weights)] per topic: the documents with the largest weight of it, descending"""
+        ids, td = self.topicDistributions()
+        n = min(int(maxDocumentsPerTopic), ids.size)
+        out = []
+        for t in range(self.k):
+            top = np.argsort(-td[:, t], kind="stable")[:n]
+            out.append((ids[top], td[top, t]))
+        return out
+
+    def save(self, path, overwrite=False):
+        """Write this model as a Spark mllib DistributedLDAModel directory (stc.io.save_distributed)."""
+        from . import io
+
+        d = self._d
+        io.save_distributed(path, d["doc_ids"], d["doc_topics"], d["topics"], d["edges"], d["alpha"], d["eta"],
+                            gamma_shape=d["gamma_shape"], iteration_times=d["iteration_times"], overwrite=overwrite)
 
     @staticmethod
     def load(path) -> "DistributedLDAModel":
@@ -609,8 +759,45 @@ class OnlineLDAOptimizer:
         return self
 
 
+class EMLDAOptimizer:
+    """mllib EMLDAOptimizer (``new EMLDAOptimizer``, LDAClustering.scala:41).  keepLastCheckpoint concerns
+    Spark's RDD lineage only: accepted and inert here."""
+
+    def __init__(self):
+        self.keepLastCheckpoint = True
+
+    def getKeepLastCheckpoint(self):
+        return self.keepLastCheckpoint
+
+    def setKeepLastCheckpoint(self, b):
+        self.keepLastCheckpoint = bool(b)
+        return self
+
+
+def em_concentrations(k, docConcentration=-1.0, topicConcentration=-1.0):
+    """[U] EMLDAOptimizer.initialize's parameter rules → (α, η): a symmetric docConcentration (a scalar or k
+    equal values; −1 ⇒ 50/k + 1) and a topicConcentration (−1 ⇒ 1.1), both > 1 otherwise."""
+    a = np.atleast_1d(np.asarray(-1.0 if docConcentration is None else docConcentration, np.float64))
+    if a.size not in (1, int(k)):
+        raise ValueError(f"docConcentration must have 1 or k = {k} values but has {a.size}")
+    if np.any(a != a[0]):
+        raise ValueError("EMLDAOptimizer currently only supports symmetric document-topic priors")
+    alpha = float(a[0])
+    eta = float(-1.0 if topicConcentration is None else topicConcentration)
+    if alpha == -1.0:
+        alpha = 50.0 / int(k) + 1.0
+    elif not alpha > 1.0:
+        raise ValueError(f"For EM optimizer, docConcentration must be > 1.0 (or -1 for auto) but was set to {alpha}")
+    if eta == -1.0:
+        eta = 1.1
+    elif not eta > 1.0:
+        raise ValueError(f"For EM optimizer, topicConcentration must be > 1.0 (or -1 for auto) but was set to {eta}")
+    return alpha, eta
+
+
 class MllibLDA:
-    """mllib.clustering.LDA as driven at LDAClustering.scala:37-61 (online optimizer only)."""
+    """mllib.clustering.LDA as driven at LDAClustering.scala:37-61: the optimizer switch of :40-46 takes
+    ``"em"`` / ``EMLDAOptimizer`` (the reference's default) or ``"online"`` / ``OnlineLDAOptimizer``."""
 
     def __init__(self, ctx: Context | None = None):
         self.k, self.maxIterations, self.docConcentration, self.topicConcentration = 10, 20, -1.0, -1.0
@@ -622,10 +809,9 @@ class MllibLDA:
 
     def setOptimizer(self, opt):
         if isinstance(opt, str):
-            if opt.lower() != "online":
-                raise ValueError(f"Only em, online are supported but got {opt}." if opt.lower() != "em"
-                                 else "optimizer 'em' (EMLDAOptimizer) is out of scope for this build")
-            opt = OnlineLDAOptimizer()
+            if opt.lower() not in ("em", "online"):
+                raise ValueError(f"Only em, online are supported but got {opt}.")
+            opt = EMLDAOptimizer() if opt.lower() == "em" else OnlineLDAOptimizer()
         self.optimizer = opt
         return self
 
@@ -657,8 +843,36 @@ class MllibLDA:
         self.seed = int(s)
         return self
 
-    def run(self, corpus) -> LDAModel:
+    def _run_em(self, corpus) -> DistributedLDAModel:
+        """EMLDAOptimizer.initialize, maxIterations × next, getLDAModel (a DistributedLDAModel)"""
+        import time
+
+        alpha, eta = em_concentrations(self.k, self.docConcentration, self.topicConcentration)
+        ctx = self._ctx or Context.get()
+        if isinstance(corpus, DeviceCsr):
+            dev, host = corpus, corpus.download()
+        else:
+            dev, host = DeviceCsr.upload(ctx, corpus, L.STC_F64), corpus
+        try:
+            em = EmHandle(ctx, dev, self.k, alpha, eta)
+        finally:
+            if dev is not corpus:
+                dev.free()
+        em.init_random(self.seed)
+        ctx.synchronize()
+        self.iterationTimes = []
+        for _ in range(self.maxIterations):
+            t0 = time.perf_counter()
+            em.next(1)
+            ctx.synchronize()
+            self.iterationTimes.append(time.perf_counter() - t0)
+        return DistributedLDAModel._from_em(em, host, self.iterationTimes)
+
+    def run(self, corpus):
+        """lda.run(corpus): a ``DistributedLDAModel`` under the EM optimizer, an ``LDAModel`` under the online one"""
         o = self.optimizer
+        if isinstance(o, EMLDAOptimizer):
+            return self._run_em(corpus)
         ctx = self._ctx or Context.get()
         d, _ = _as_device(ctx, corpus, _DTYPES[self.dtype])
         total = int(ctx.allreduce([float(d.num_rows)])[0]) if ctx.n_ranks > 1 else d.num_rows

@@ -1,0 +1,104 @@
+#!/usr/bin/env python3
+"""Time the EM optimizer's iteration (stc_em_next) — one JSON line per case.
+
+Cases:
+  golden   the reference's saved EN model's graph (tests/golden/LdaModel_EN_1591049082850: 51 documents,
+           V = 39,380, 253,368 edges) at k = 5, from its saved state.  The model's own metadata records the
+           reference's iterationTimes for exactly this graph (median 0.702 s per iteration over its 50, on an
+           unknown PC under Spark local[*]); the line reports the ratio with that caveat.
+  zipf     stc.synth.zipf_corpus, 100k documents × 200 tokens, V = 2^18, k = 100, from init_random.
+
+Per case: --warmup (3) untimed iterations, then --iters (20) timed as ONE enqueued batch between two stream
+synchronisations (an iteration has no host round trip), repeated --repeats (5) times; the line carries the
+median and the spread.  edges·k per second and algorithmic bytes per second follow from the median.
+Algorithmic bytes per iteration = for each of the two passes, the edge arrays once (4 B index + 8 B count
+per edge) plus one gathered k-row (8k B) per edge: 2·E·(12 + 8k).
+
+    python tools/bench_em.py [--case golden|zipf|all] [--iters 20] [--warmup 3] [--repeats 5]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, "spark-text-clustering_amd"), ROOT]
+
+GOLDEN_MODEL = os.path.join(ROOT, "tests", "golden", "LdaModel_EN_1591049082850")
+
+
+def golden_case(stc, ctx):
+    m = stc.io.load_distributed(GOLDEN_MODEL)
+    src, term, cnt = m["edges"]
+    row = np.searchsorted(m["doc_ids"], src)
+    order = np.argsort(row, kind="stable")
+    indptr = np.zeros(m["doc_ids"].size + 1, np.int64)
+    np.cumsum(np.bincount(row, minlength=m["doc_ids"].size), out=indptr[1:])
+    corpus = stc.CsrMatrix(indptr, term[order], cnt[order], m["vocab_size"])
+    dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
+    h = stc.EmHandle(ctx, dev, m["k"], float(m["alpha"][0]), m["eta"])
+    dev.free()
+    h.set_state(m["doc_topics"], m["topics"])
+    ref = float(np.median(m["iteration_times"]))
+    return h, {"case": "golden", "reference_s_per_iteration": ref,
+               "reference_note": "median of the saved model's 50 iterationTimes; unknown PC, Spark local[*]"}
+
+
+def zipf_case(stc, ctx, docs, tokens, vocab, k):
+    from stc import synth
+
+    corpus = synth.zipf_corpus(docs, tokens, vocab, workers=min(16, os.cpu_count() or 1))
+    dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
+    h = stc.EmHandle(ctx, dev, k)
+    dev.free()
+    h.init_random(1)
+    return h, {"case": "zipf", "docs": docs, "tokens_per_doc": tokens}
+
+
+def measure(ctx, h, info, iters, warmup, repeats):
+    h.next(warmup)
+    ctx.synchronize()
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        h.next(iters)
+        ctx.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3 / iters)
+    med = float(np.median(ms))
+    E, k = h.num_edges, h.k
+    algo_bytes = 2.0 * E * (12 + 8 * k)
+    ll, lp = h.log_likelihood()
+    out = dict(info, n_docs=h.num_docs, vocab=h.vocab_size, k=k, edges=E, iters=iters, warmup=warmup, repeats=repeats,
+               ms_per_iteration=med, ms_per_iteration_min=float(min(ms)), ms_per_iteration_max=float(max(ms)),
+               edges_k_per_s=E * k / (med * 1e-3), algorithmic_bytes_per_iteration=algo_bytes,
+               algorithmic_bytes_per_s=algo_bytes / (med * 1e-3), log_likelihood=ll, log_prior=lp)
+    if "reference_s_per_iteration" in info:
+        out["speedup_vs_reference"] = info["reference_s_per_iteration"] / (med * 1e-3)
+    return out
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--case", choices=("golden", "zipf", "all"), default="all")
+    p.add_argument("--iters", type=int, default=20)
+    p.add_argument("--warmup", type=int, default=3)
+    p.add_argument("--repeats", type=int, default=5)
+    p.add_argument("--docs", type=int, default=100_000)
+    p.add_argument("--tokens", type=int, default=200)
+    p.add_argument("--vocab", type=int, default=1 << 18)
+    p.add_argument("--k", type=int, default=100)
+    a = p.parse_args()
+    import stc
+
+    ctx = stc.Context.get(0)
+    for case in (("golden", "zipf") if a.case == "all" else (a.case,)):
+        h, info = golden_case(stc, ctx) if case == "golden" else zipf_case(stc, ctx, a.docs, a.tokens, a.vocab, a.k)
+        print(json.dumps(measure(ctx, h, info, a.iters, a.warmup, a.repeats)), flush=True)
+        h.close()
+
+
+if __name__ == "__main__":
+    main()
