@@ -13,6 +13,9 @@
  *                               CoreNLP front-end at LDAClustering.scala:116-139 is out of scope)
  *   stc_hashing_tf[_dev]        [U] mllib.feature.HashingTF.transform / murmur3Hash — the slot of
  *                               the vocab-indexed counting at LDAClustering.scala:154-167
+ *   stc_cv_*                    [U] ml.feature.CountVectorizer / CountVectorizerModel — the vocabulary-indexed
+ *                               counting itself: fit at LDAClustering.scala:143-171, the saved vocabulary's
+ *                               lookup + counts at LDALoader.scala:83-105
  *   stc_idf_fit                 IDF(minDocFreq).fit(tf).idf — LDAClustering.scala:177
  *   stc_idf_transform           tf × idf (+ the 0 → 1e-4 floor) — LDAClustering.scala:180-192
  *   stc_lda_create / set_corpus new LDA().setOptimizer(online)...setK... — LDAClustering.scala:37-54
@@ -154,6 +157,48 @@ int stc_hashing_tf_tokens(stc_ctx* ctx, const stc_dtok* tokens, int32_t num_feat
 /* raw per-token bucket indices (test hook for K1): idx_out[n_tok] */
 int stc_hash_tokens(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off,
                     int64_t n_tok, int32_t num_features, int hash_variant, int32_t* idx_out);
+
+/* ---- CountVectorizer ([U] ml.feature.CountVectorizer → CountVectorizerModel) -----------------
+ * Tokens in HashingTF's layout (utf8, tok_off, doc_off).  Two tokens are the same term iff their bytes are
+ * equal; the empty string is a term like any other.
+ * fit: for every distinct term, count = its occurrences and df = the documents holding it (n_docs counts
+ * empty documents).  With minDf = min_df >= 1 ? min_df : min_df * n_docs and maxDf likewise (fp64, as Spark),
+ * the terms with minDf <= df <= maxDf are ordered by count descending, then by their UTF-8 bytes ascending
+ * (unsigned, a proper prefix first: Spark leaves ties to the partitioning, this fixes them so the vocabulary
+ * does not depend on document order), and the first min(vocab_size, #terms) are kept.  Spark's defaults:
+ * vocab_size 2^18, min_df 1.0, max_df 2^63-1.  STC_ERR_INVALID_ARG: vocab_size <= 0, a negative threshold,
+ * maxDf < minDf, or nothing kept ("The vocabulary size should be > 0. Lower minDF as necessary.").
+ * transform: row d holds, ascending, the indices of the vocabulary terms whose count c in document d is
+ * >= (min_tf >= 1 ? min_tf : tokenCount_d * min_tf), tokenCount_d counting every token of the document, those
+ * outside the vocabulary too; the value is c (1.0 when binary).  The matrix has n_terms columns and the
+ * guarantees of a HashingTF output.  Spark's defaults: min_tf 1.0, binary 0.
+ * At most 2^31-1 tokens per call.  Bitwise reproducible.  Single device: every call on a context connected
+ * to other ranks returns STC_ERR_STATE.  Test knob: STC_CV_HASH_BITS=n (1..64, read when a model is made and
+ * kept in it) masks the internal 64-bit term hash to its low n bits; no result depends on it. */
+typedef struct stc_cvm stc_cvm; /* CountVectorizerModel on the device; belongs to its stc_ctx as an stc_dcsr does */
+int stc_cv_fit(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off /* n_tok+1 */,
+               int64_t n_tok, const int64_t* doc_off /* n_docs+1 */, int64_t n_docs, int64_t vocab_size,
+               double min_df, double max_df, stc_cvm** out);
+int stc_cv_fit_tokens(stc_ctx* ctx, const stc_dtok* tokens, int64_t vocab_size, double min_df, double max_df,
+                      stc_cvm** out);
+/* a model from a list of terms, index = position; a term given twice: STC_ERR_INVALID_ARG naming it */
+int stc_cv_from_vocabulary(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes,
+                           const int64_t* term_off /* n_terms+1 */, int64_t n_terms, stc_cvm** out);
+int stc_cv_shape(const stc_cvm* model, int64_t* n_terms_out, int64_t* n_bytes_out);
+/* utf8_out[n_bytes], term_off_out[n_terms+1], count_out[n_terms], df_out[n_terms]; any may be NULL; count and
+ * df are 0 for a model made from a list */
+int stc_cv_get(stc_ctx* ctx, const stc_cvm* model, uint8_t* utf8_out, int64_t* term_off_out,
+               int64_t* count_out, int64_t* df_out);
+/* idx_out[n_tok]: each token's vocabulary index, -1 when it is not in the vocabulary */
+int stc_cv_index_of(stc_ctx* ctx, const stc_cvm* model, const uint8_t* utf8, int64_t n_bytes,
+                    const int64_t* tok_off, int64_t n_tok, int32_t* idx_out);
+int stc_cv_transform_dev(stc_ctx* ctx, const stc_cvm* model, const uint8_t* utf8, int64_t n_bytes,
+                         const int64_t* tok_off, int64_t n_tok, const int64_t* doc_off, int64_t n_docs,
+                         double min_tf, int binary, int value_dtype, stc_dcsr** out);
+int stc_cv_transform_tokens(stc_ctx* ctx, const stc_cvm* model, const stc_dtok* tokens, double min_tf,
+                            int binary, int value_dtype, stc_dcsr** out);
+/* waits for queued work, then frees the device memory (valid after stc_destroy of the context) */
+int stc_cv_free(stc_cvm* model);
 
 /* ---- Tokenizer (K0) ----------------------------------------------------------------------
  * Document d is the UTF-8 string text[text_off[d] .. text_off[d+1]).  Output: Spark's

@@ -9,7 +9,7 @@
  *       -L../spark-text-clustering_amd/stc -lstc -Wl,-rpath,'$ORIGIN' -o libstcjni.so
  *
  * Conventions:
- *   - handles (stc_ctx*, stc_dcsr*, stc_lda*) cross as jlong;
+ *   - handles (stc_ctx*, stc_dcsr*, stc_lda*, stc_cvm*, …) cross as jlong;
  *   - a non-zero status becomes a Java exception with stc_last_error() as the message:
  *     STC_ERR_INVALID_ARG → IllegalArgumentException, anything else → IllegalStateException;
  *   - host arrays are pinned with Get<Type>ArrayElements for the duration of the call (the library
@@ -33,6 +33,7 @@
 #define LDA(h) ((stc_lda*)(intptr_t)(h))
 #define GRP(h) ((stc_group*)(intptr_t)(h))
 #define EM(h) ((stc_em*)(intptr_t)(h))
+#define CVM(h) ((stc_cvm*)(intptr_t)(h))
 
 static int check(JNIEnv* env, int st) {
   if (st == STC_OK) return 0;
@@ -681,6 +682,113 @@ JNIEXPORT jdoubleArray JNICALL FN(emLogLikelihood)(JNIEnv* env, jclass c, jlong 
   if (out) (*env)->SetDoubleArrayRegion(env, out, 0, 2, r);
   return out;
 }
+
+/* ---- CountVectorizer (stc_cv_*: ml.feature.CountVectorizer / CountVectorizerModel) ---------------- */
+JNIEXPORT jlong JNICALL FN(cvFit)(JNIEnv* env, jclass c, jlong ctx, jbyteArray utf8, jlongArray tok_off,
+                                  jlongArray doc_off, jlong vocab_size, jdouble min_df, jdouble max_df) {
+  stc_cvm* out = NULL;
+  jbyte* u = PIN(jbyte, Byte, utf8);
+  jlong* to = PIN(jlong, Long, tok_off);
+  jlong* dof = PIN(jlong, Long, doc_off);
+  int st = stc_cv_fit(CTX(ctx), (const uint8_t*)u, LEN(utf8), (const int64_t*)to, LEN(tok_off) - 1,
+                      (const int64_t*)dof, LEN(doc_off) - 1, vocab_size, min_df, max_df, &out);
+  UNPIN(Long, doc_off, dof, JNI_ABORT);
+  UNPIN(Long, tok_off, to, JNI_ABORT);
+  UNPIN(Byte, utf8, u, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT jlong JNICALL FN(cvFitTokens)(JNIEnv* env, jclass c, jlong ctx, jlong tokens, jlong vocab_size,
+                                        jdouble min_df, jdouble max_df) {
+  stc_cvm* out = NULL;
+  if (check(env, stc_cv_fit_tokens(CTX(ctx), (const stc_dtok*)(intptr_t)tokens, vocab_size, min_df, max_df, &out)))
+    return 0;
+  return (jlong)(intptr_t)out;
+}
+
+/* term j = utf8[termOff[j], termOff[j+1]); index = position */
+JNIEXPORT jlong JNICALL FN(cvFromVocabulary)(JNIEnv* env, jclass c, jlong ctx, jbyteArray utf8, jlongArray term_off) {
+  stc_cvm* out = NULL;
+  jbyte* u = PIN(jbyte, Byte, utf8);
+  jlong* to = PIN(jlong, Long, term_off);
+  int st = stc_cv_from_vocabulary(CTX(ctx), (const uint8_t*)u, LEN(utf8), (const int64_t*)to, LEN(term_off) - 1, &out);
+  UNPIN(Long, term_off, to, JNI_ABORT);
+  UNPIN(Byte, utf8, u, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+/* {nTerms, nBytes} */
+JNIEXPORT jlongArray JNICALL FN(cvShape)(JNIEnv* env, jclass c, jlong model) {
+  int64_t s[2] = {0, 0};
+  if (check(env, stc_cv_shape(CVM(model), &s[0], &s[1]))) return NULL;
+  jlongArray out = (*env)->NewLongArray(env, 2);
+  if (out) (*env)->SetLongArrayRegion(env, out, 0, 2, (const jlong*)s);
+  return out;
+}
+
+/* every array nullable: utf8Out nBytes, termOffOut nTerms + 1, countOut nTerms, dfOut nTerms */
+JNIEXPORT void JNICALL FN(cvGet)(JNIEnv* env, jclass c, jlong ctx, jlong model, jbyteArray utf8_out,
+                                 jlongArray term_off_out, jlongArray count_out, jlongArray df_out) {
+  int64_t s[2] = {0, 0};
+  if (check(env, stc_cv_shape(CVM(model), &s[0], &s[1])) || NEED(utf8_out, s[1], "cvGet utf8Out") ||
+      NEED(term_off_out, s[0] + 1, "cvGet termOffOut") || NEED(count_out, s[0], "cvGet countOut") ||
+      NEED(df_out, s[0], "cvGet dfOut"))
+    return;
+  jbyte* u = PIN(jbyte, Byte, utf8_out);
+  jlong* to = PIN(jlong, Long, term_off_out);
+  jlong* cn = PIN(jlong, Long, count_out);
+  jlong* df = PIN(jlong, Long, df_out);
+  int st = stc_cv_get(CTX(ctx), CVM(model), (uint8_t*)u, (int64_t*)to, (int64_t*)cn, (int64_t*)df);
+  UNPIN(Long, df_out, df, 0);
+  UNPIN(Long, count_out, cn, 0);
+  UNPIN(Long, term_off_out, to, 0);
+  UNPIN(Byte, utf8_out, u, 0);
+  check(env, st);
+}
+
+/* idxOut[nTok]: the vocabulary index of every token, −1 outside the vocabulary */
+JNIEXPORT void JNICALL FN(cvIndexOf)(JNIEnv* env, jclass c, jlong ctx, jlong model, jbyteArray utf8,
+                                     jlongArray tok_off, jintArray idx_out) {
+  if (NEED(idx_out, LEN(tok_off) - 1, "cvIndexOf idxOut")) return;
+  jbyte* u = PIN(jbyte, Byte, utf8);
+  jlong* to = PIN(jlong, Long, tok_off);
+  jint* ix = PIN(jint, Int, idx_out);
+  int st = stc_cv_index_of(CTX(ctx), CVM(model), (const uint8_t*)u, LEN(utf8), (const int64_t*)to, LEN(tok_off) - 1,
+                           (int32_t*)ix);
+  UNPIN(Int, idx_out, ix, 0);
+  UNPIN(Long, tok_off, to, JNI_ABORT);
+  UNPIN(Byte, utf8, u, JNI_ABORT);
+  check(env, st);
+}
+
+JNIEXPORT jlong JNICALL FN(cvTransformDev)(JNIEnv* env, jclass c, jlong ctx, jlong model, jbyteArray utf8,
+                                           jlongArray tok_off, jlongArray doc_off, jdouble min_tf, jboolean binary,
+                                           jint dtype) {
+  stc_dcsr* out = NULL;
+  jbyte* u = PIN(jbyte, Byte, utf8);
+  jlong* to = PIN(jlong, Long, tok_off);
+  jlong* dof = PIN(jlong, Long, doc_off);
+  int st = stc_cv_transform_dev(CTX(ctx), CVM(model), (const uint8_t*)u, LEN(utf8), (const int64_t*)to,
+                                LEN(tok_off) - 1, (const int64_t*)dof, LEN(doc_off) - 1, min_tf, binary, dtype, &out);
+  UNPIN(Long, doc_off, dof, JNI_ABORT);
+  UNPIN(Long, tok_off, to, JNI_ABORT);
+  UNPIN(Byte, utf8, u, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT jlong JNICALL FN(cvTransformTokens)(JNIEnv* env, jclass c, jlong ctx, jlong model, jlong tokens,
+                                              jdouble min_tf, jboolean binary, jint dtype) {
+  stc_dcsr* out = NULL;
+  if (check(env, stc_cv_transform_tokens(CTX(ctx), CVM(model), (const stc_dtok*)(intptr_t)tokens, min_tf, binary,
+                                         dtype, &out)))
+    return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT void JNICALL FN(cvFree)(JNIEnv* env, jclass c, jlong model) { check(env, stc_cv_free(CVM(model))); }
 
 /* ---- one process, N devices (stc_group) ---------------------------------------------------------- */
 /* the same parameters as ldaCreate, plus the device ids */

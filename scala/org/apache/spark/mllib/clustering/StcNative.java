@@ -122,6 +122,26 @@ public final class StcNative {
   /** {logLikelihood, logPrior} */
   public static native double[] emLogLikelihood(long em);
 
+  // ---- CountVectorizer (stc_cv_*: ml.feature.CountVectorizer / CountVectorizerModel; tokens as for HashingTF)
+  /** fit: the vocabSize most frequent terms with minDf <= df <= maxDf (ties by the terms' UTF-8 bytes) */
+  public static native long cvFit(long ctx, byte[] utf8, long[] tokOff, long[] docOff, long vocabSize, double minDf,
+                                  double maxDf);
+  public static native long cvFitTokens(long ctx, long tokens, long vocabSize, double minDf, double maxDf);
+  /** term j = utf8[termOff[j], termOff[j+1]), index = position; a term given twice: IllegalArgumentException */
+  public static native long cvFromVocabulary(long ctx, byte[] utf8, long[] termOff);
+  /** {nTerms, nBytes} of the model */
+  public static native long[] cvShape(long model);
+  /** every array nullable: utf8Out nBytes, termOffOut nTerms + 1, countOut nTerms, dfOut nTerms */
+  public static native void cvGet(long ctx, long model, byte[] utf8Out, long[] termOffOut, long[] countOut,
+                                  long[] dfOut);
+  /** idxOut[nTok]: each token's vocabulary index, −1 outside the vocabulary */
+  public static native void cvIndexOf(long ctx, long model, byte[] utf8, long[] tokOff, int[] idxOut);
+  public static native long cvTransformDev(long ctx, long model, byte[] utf8, long[] tokOff, long[] docOff,
+                                           double minTf, boolean binary, int valueDtype);
+  public static native long cvTransformTokens(long ctx, long model, long tokens, double minTf, boolean binary,
+                                              int valueDtype);
+  public static native void cvFree(long model);
+
   // ---- host helpers (pure Java): Spark vectors → CSR arrays
   /** CSR of sparse or dense rows: {indptr long[n+1], indices int[nnz], values double[nnz]} */
   public static Object[] toCsr(org.apache.spark.mllib.linalg.Vector[] rows) {

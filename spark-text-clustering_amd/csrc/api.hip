@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <unordered_set>
 
+#include "count_vectorizer.h"
 #include "lda_em.h"
 #include "lda_kernels.h"
 
@@ -2575,6 +2576,137 @@ int stc_em_log_likelihood(stc_em* m, double* log_likelihood_out, double* log_pri
     STC_REQUIRE(m, "em");
     em::log_likelihood(*m, log_likelihood_out, log_prior_out);
   });
+}
+
+// ---- CountVectorizer (count_vectorizer.hip) --------------------------------------------------
+namespace {
+void cv_view_upload(const TokenUpload& u, int64_t n_tok, int64_t n_docs, cv::TokView& v) {
+  v.utf8 = u.utf8.as<uint8_t>();
+  v.off64 = u.tok_off.as<int64_t>();
+  v.n_tok = n_tok;
+  v.doc_off = u.doc_off.as<int64_t>();
+  v.n_docs = n_docs;
+  v.max_doc = u.max_doc;
+}
+void cv_view_tokens(const stc_dtok& t, cv::TokView& v) {
+  v.utf8 = t.utf8.as<uint8_t>();
+  if (t.off32) v.off32 = t.tok_off.as<uint32_t>();
+  else v.off64 = t.tok_off.as<int64_t>();
+  v.n_tok = t.n_tok;
+  v.doc_off = t.doc_off.as<int64_t>();
+  v.n_docs = t.n_docs;
+  v.max_doc = t.max_doc;
+}
+}  // namespace
+
+int stc_cv_fit(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off, int64_t n_tok,
+               const int64_t* doc_off, int64_t n_docs, int64_t vocab_size, double min_df, double max_df,
+               stc_cvm** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && doc_off && out, "ctx/doc_off/out");
+    ctx->use();
+    TokenUpload u;
+    upload_tokens(*ctx, u, utf8, n_bytes, tok_off, n_tok, doc_off, n_docs);
+    wait_stream(*ctx, ctx->stream);
+    cv::TokView v;
+    cv_view_upload(u, n_tok, n_docs, v);
+    *out = cv::fit(*ctx, v, vocab_size, min_df, max_df);
+  });
+}
+
+int stc_cv_fit_tokens(stc_ctx* ctx, const stc_dtok* tokens, int64_t vocab_size, double min_df, double max_df,
+                      stc_cvm** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && tokens && out, "ctx/tokens/out");
+    STC_REQUIRE(tokens->ctx == ctx, "tokens were uploaded on another stc_ctx");
+    cv::TokView v;
+    cv_view_tokens(*tokens, v);
+    *out = cv::fit(*ctx, v, vocab_size, min_df, max_df);
+  });
+}
+
+int stc_cv_from_vocabulary(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* term_off,
+                           int64_t n_terms, stc_cvm** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && out, "ctx/out");
+    *out = cv::from_vocabulary(*ctx, utf8, n_bytes, term_off, n_terms);
+  });
+}
+
+int stc_cv_shape(const stc_cvm* model, int64_t* n_terms_out, int64_t* n_bytes_out) {
+  return guard([&] {
+    STC_REQUIRE(model, "model");
+    if (n_terms_out) *n_terms_out = model->n_terms;
+    if (n_bytes_out) *n_bytes_out = model->n_bytes;
+  });
+}
+
+int stc_cv_get(stc_ctx* ctx, const stc_cvm* model, uint8_t* utf8_out, int64_t* term_off_out, int64_t* count_out,
+               int64_t* df_out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model, "ctx/model");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    cv::get(*ctx, *model, utf8_out, term_off_out, count_out, df_out);
+  });
+}
+
+int stc_cv_index_of(stc_ctx* ctx, const stc_cvm* model, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off,
+                    int64_t n_tok, int32_t* idx_out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model && (idx_out || n_tok == 0), "ctx/model/idx_out");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    ctx->use();
+    TokenUpload u;
+    upload_tokens(*ctx, u, utf8, n_bytes, tok_off, n_tok, nullptr, 0);
+    wait_stream(*ctx, ctx->stream);
+    cv::TokView v;
+    cv_view_upload(u, n_tok, 0, v);
+    v.doc_off = nullptr;
+    cv::index_of(*ctx, *model, v, idx_out);
+  });
+}
+
+int stc_cv_transform_dev(stc_ctx* ctx, const stc_cvm* model, const uint8_t* utf8, int64_t n_bytes,
+                         const int64_t* tok_off, int64_t n_tok, const int64_t* doc_off, int64_t n_docs, double min_tf,
+                         int binary, int value_dtype, stc_dcsr** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model && doc_off && out, "ctx/model/doc_off/out");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    STC_REQUIRE(value_dtype == STC_F32 || value_dtype == STC_F64, "value_dtype");
+    ctx->use();
+    TokenUpload u;
+    upload_tokens(*ctx, u, utf8, n_bytes, tok_off, n_tok, doc_off, n_docs);
+    wait_stream(*ctx, ctx->stream);
+    auto m = std::make_unique<stc_dcsr>();
+    m->ctx = ctx;
+    m->device = ctx->device;
+    cv::TokView v;
+    cv_view_upload(u, n_tok, n_docs, v);
+    cv::transform(*ctx, *model, v, min_tf, binary, value_dtype, *m);
+    wait_stream(*ctx, ctx->stream);  // the uploaded tokens are freed on return
+    *out = m.release();
+  });
+}
+
+int stc_cv_transform_tokens(stc_ctx* ctx, const stc_cvm* model, const stc_dtok* tokens, double min_tf, int binary,
+                            int value_dtype, stc_dcsr** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model && tokens && out, "ctx/model/tokens/out");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    STC_REQUIRE(tokens->ctx == ctx, "tokens were uploaded on another stc_ctx");
+    STC_REQUIRE(value_dtype == STC_F32 || value_dtype == STC_F64, "value_dtype");
+    auto m = std::make_unique<stc_dcsr>();
+    m->ctx = ctx;
+    m->device = ctx->device;
+    cv::TokView v;
+    cv_view_tokens(*tokens, v);
+    cv::transform(*ctx, *model, v, min_tf, binary, value_dtype, *m);
+    *out = m.release();
+  });
+}
+
+int stc_cv_free(stc_cvm* model) {
+  return guard([&] { cv::destroy(model); });
 }
 
 }  // extern "C"

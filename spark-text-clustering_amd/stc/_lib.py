@@ -93,6 +93,15 @@ SIGNATURES = {
     "stc_tokens_upload": (_int, [_p, _pu8, _i64, _pi64, _i64, _pi64, _i64, C.POINTER(_p)]),
     "stc_tokens_free": (_int, [_p]),
     "stc_hashing_tf_tokens": (_int, [_p, _p, _i32, _int, _int, _int, C.POINTER(_p)]),
+    "stc_cv_fit": (_int, [_p, _pu8, _i64, _pi64, _i64, _pi64, _i64, _i64, _dbl, _dbl, C.POINTER(_p)]),
+    "stc_cv_fit_tokens": (_int, [_p, _p, _i64, _dbl, _dbl, C.POINTER(_p)]),
+    "stc_cv_from_vocabulary": (_int, [_p, _pu8, _i64, _pi64, _i64, C.POINTER(_p)]),
+    "stc_cv_shape": (_int, [_p, _pi64, _pi64]),
+    "stc_cv_get": (_int, [_p, _p, _pu8, _pi64, _pi64, _pi64]),
+    "stc_cv_index_of": (_int, [_p, _p, _pu8, _i64, _pi64, _i64, _pi32]),
+    "stc_cv_transform_dev": (_int, [_p, _p, _pu8, _i64, _pi64, _i64, _pi64, _i64, _dbl, _int, _int, C.POINTER(_p)]),
+    "stc_cv_transform_tokens": (_int, [_p, _p, _p, _dbl, _int, _int, C.POINTER(_p)]),
+    "stc_cv_free": (_int, [_p]),
     "stc_tokenize": (_int, [_p, _pu8, _i64, _pi64, _i64, _pu8, _i64, _pi64, _pi64, _pi64, _pi64]),
     "stc_tokenize_hashing_tf_dev": (_int, [_p, _pu8, _i64, _pi64, _i64, _i32, _int, _int, _int,
                                            C.POINTER(_p)]),

@@ -243,3 +243,25 @@ def load_distributed(path):
             "alpha": np.asarray(meta["docConcentration"], np.float64), "eta": float(meta["topicConcentration"]),
             "gamma_shape": float(meta.get("gammaShape", 100.0)),
             "iteration_times": np.asarray(meta.get("iterationTimes", []), np.float64), "k": k, "vocab_size": V}
+
+
+def save_vocabulary(path, terms):
+    """The reference's vocabulary file (LDAClustering.scala:71-72): one line, ``vocabArray.mkString(",")``.
+    A term holding a comma or a line break could not be read back and raises ValueError."""
+    terms = [t.decode("utf-8") if isinstance(t, (bytes, bytearray)) else str(t) for t in terms]
+    for t in terms:
+        if "," in t or "\n" in t or "\r" in t:
+            raise ValueError(f"the vocabulary file format cannot hold the term {t!r} (comma or line break)")
+    with open(path, "w", encoding="utf-8", newline="") as f:
+        f.write(",".join(terms))
+
+
+def load_vocabulary(path):
+    """Reads it as LDALoader.scala:43 does: the first line, ``split(",")`` (Java drops trailing empty strings)."""
+    with open(path, encoding="utf-8", newline="") as f:
+        text = f.read()
+    lines = text.splitlines()
+    terms = lines[0].split(",") if lines else [""]
+    while terms and terms[-1] == "":
+        terms.pop()
+    return terms
