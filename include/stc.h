@@ -10,7 +10,10 @@
  *
  *   stc_tokenize[_hashing_tf_dev] [U] ml.feature.Tokenizer (toLowerCase.split("\\s")), the step in
  *                               front of HashingTF (the reference's own
- *                               CoreNLP front-end at LDAClustering.scala:116-139 is out of scope)
+ *                               CoreNLP lemmatiser at LDAClustering.scala:116-120 is out of scope)
+ *   stc_prep_*                  the reference's own steps behind that lemmatiser: LDAUtil.filterSpecialCharacters,
+ *                               OpenNLP SimpleTokenizer, the stop-word filter and OpenNLP PorterStemmer —
+ *                               LDAClustering.scala:121-139 (training), :221-238 (scoring)
  *   stc_hashing_tf[_dev]        [U] mllib.feature.HashingTF.transform / murmur3Hash — the slot of
  *                               the vocab-indexed counting at LDAClustering.scala:154-167
  *   stc_cv_*                    [U] ml.feature.CountVectorizer / CountVectorizerModel — the vocabulary-indexed
@@ -222,6 +225,50 @@ int stc_tokenize(stc_ctx* ctx, const uint8_t* text, int64_t n_bytes, const int64
 int stc_tokenize_hashing_tf_dev(stc_ctx* ctx, const uint8_t* text, int64_t n_bytes,
                                 const int64_t* text_off, int64_t n_docs, int32_t num_features,
                                 int binary, int hash_variant, int value_dtype, stc_dcsr** out);
+
+/* ---- Text preprocessing (the reference's own front end behind its lemmatiser) ---------------
+ * filterSpecialCharacters → OpenNLP SimpleTokenizer → drop stop words → OpenNLP PorterStemmer, what the reference
+ * runs on every book between CoreNLP's lemmatiser and the vocabulary (LDAClustering.scala:121-139, :221-238).  A
+ * document is a UTF-8 string; a "char" is a Java char (a UTF-16 code unit; every BMP code point is one char).
+ * 1. Strip.  A set of BMP code points counts as white space (the reference replaces each by one space, which
+ *    yields the same tokens).  Default (strip_cp NULL, n_strip -1): what the regex class of
+ *    LDAClustering.scala:283-284 denotes under java.util.regex — U+0020–U+002D (its trailing "' ' '-' '-'" is that
+ *    range), . : ; ? @ ^ _ `, U+00AB, U+00BB, U+2019, U+201D, U+2212.  (U+201C, U+2018 and / are not in it.)
+ * 2. SimpleTokenizer (OpenNLP 1.6.0 tokenizePos).  A char is WHITESPACE (Character.isWhitespace or category Zs; the
+ *    stripped chars too), ALPHABETIC (Character.isLetter, category L*), NUMERIC (Character.isDigit, category Nd) or
+ *    OTHER.  A token is a maximal run of non-WHITESPACE chars of one class; an OTHER run also ends where the char
+ *    changes ("--" is one token, "-/" two).  No lower-casing.  A document is tokenised on its own.  The classes come
+ *    from a generated table of the BMP (csrc/class_table.h: Java 8 is Unicode 6.2; code points assigned later are
+ *    classed by the generator's newer database — parity unpinned).  The one departure: a code point >= U+10000 is
+ *    always one OTHER token of its own (Java sees two unpaired-looking surrogate chars, which UTF-8 cannot carry).
+ * 3. Stop words.  A token whose bytes equal a listed word is dropped: exact, case-sensitive, before stemming (so
+ *    "being" → "be" survives although "be" is listed).  An empty list drops nothing.
+ * 4. Porter stemmer (opennlp.tools.stemmer.PorterStemmer.stem(String), 1.6.0, Lucene's): tokens of <= 2 chars
+ *    unchanged; only a e i o u are vowels, y after a consonant too, every other char (capitals, digits, non-ASCII)
+ *    is a consonant; Lucene's step1–step6 with its tables (bli → ble and logi → log present, ion only after s or
+ *    t, each switch case of steps 3–5 done after its first matching suffix whether replaced or not); doublec and
+ *    cvc compare chars, not bytes.  The stem is never longer than the token and never empty.
+ * 5. Every input document yields a row of the result, possibly without tokens.  (The reference drops the empty
+ *    documents and renumbers the rest: the caller's job.)
+ * The result is an stc_dtok like an upload's (stc_cv_fit_tokens, stc_cv_transform_tokens and stc_hashing_tf_tokens
+ * take it).  Bitwise reproducible.  STC_ERR_INVALID_ARG: malformed UTF-8 in the text or the stop words (the message
+ * names the byte offset), a strip code point >= U+10000 or a surrogate, more than 2^31-1 tokens.  Single device:
+ * every call on a context connected to other ranks returns STC_ERR_STATE. */
+typedef struct stc_prep stc_prep; /* strip set + stop words + stemmer switch on the device; belongs to its stc_ctx */
+int stc_prep_create(stc_ctx* ctx, const uint32_t* strip_cp, int64_t n_strip /* NULL, -1: the reference's set */,
+                    const uint8_t* stop_utf8, int64_t n_bytes, const int64_t* stop_off /* n_stop+1 */,
+                    int64_t n_stop, int stem /* 0 none, 1 Porter */, stc_prep** out);
+int stc_prep_free(stc_prep* prep); /* valid after stc_destroy of the context */
+int stc_prep_tokens(stc_ctx* ctx, const stc_prep* prep, const uint8_t* text, int64_t n_bytes,
+                    const int64_t* text_off /* n_docs+1 */, int64_t n_docs, stc_dtok** out);
+/* sizes of device tokens (any may be NULL), and their copy to the host: utf8_out[n_bytes], tok_off_out[n_tok+1],
+ * doc_off_out[n_docs+1] (any may be NULL) */
+int stc_tokens_shape(const stc_dtok* tokens, int64_t* n_bytes, int64_t* n_tok, int64_t* n_docs);
+int stc_tokens_download(stc_ctx* ctx, const stc_dtok* tokens, uint8_t* utf8_out, int64_t* tok_off_out,
+                        int64_t* doc_off_out);
+/* the stemmer alone, each token on its own (test hook): utf8_out[n_bytes], tok_off_out[n_tok+1] */
+int stc_stem_tokens(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off, int64_t n_tok,
+                    uint8_t* utf8_out, int64_t* tok_off_out);
 
 /* ---- IDF (K3 df count, K4 idf, K5 transform) ---------------------------------------------
  * df_j = #rows with value_j > 0, m = #rows (summed over all ranks when connected);

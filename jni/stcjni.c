@@ -790,6 +790,96 @@ JNIEXPORT jlong JNICALL FN(cvTransformTokens)(JNIEnv* env, jclass c, jlong ctx, 
 
 JNIEXPORT void JNICALL FN(cvFree)(JNIEnv* env, jclass c, jlong model) { check(env, stc_cv_free(CVM(model))); }
 
+/* ---- text preprocessing (strip, SimpleTokenizer, stop words, Porter stemmer) --------------------------- */
+/* stripCp null: the reference's set; stop word j = stopUtf8[stopOff[j], stopOff[j+1]) (stopOff null: none) */
+JNIEXPORT jlong JNICALL FN(prepCreate)(JNIEnv* env, jclass c, jlong ctx, jintArray strip_cp, jbyteArray stop_utf8,
+                                       jlongArray stop_off, jboolean stem) {
+  stc_prep* out = NULL;
+  jint* sc = PIN(jint, Int, strip_cp);
+  jbyte* u = PIN(jbyte, Byte, stop_utf8);
+  jlong* so = PIN(jlong, Long, stop_off);
+  int st = stc_prep_create(CTX(ctx), (const uint32_t*)sc, strip_cp ? LEN(strip_cp) : -1, (const uint8_t*)u, LEN(stop_utf8),
+                           (const int64_t*)so, stop_off ? LEN(stop_off) - 1 : 0, stem ? 1 : 0, &out);
+  UNPIN(Long, stop_off, so, JNI_ABORT);
+  UNPIN(Byte, stop_utf8, u, JNI_ABORT);
+  UNPIN(Int, strip_cp, sc, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT void JNICALL FN(prepFree)(JNIEnv* env, jclass c, jlong prep) {
+  check(env, stc_prep_free((stc_prep*)(intptr_t)prep));
+}
+
+/* document d = text[textOff[d], textOff[d+1]); returns device tokens (tokensFree) */
+JNIEXPORT jlong JNICALL FN(prepTokens)(JNIEnv* env, jclass c, jlong ctx, jlong prep, jbyteArray text, jlongArray text_off) {
+  stc_dtok* out = NULL;
+  if (!text_off || LEN(text_off) < 1) {
+    throw_iae(env, "prepTokens: textOff needs nDocs + 1 entries");
+    return 0;
+  }
+  jbyte* t = PIN(jbyte, Byte, text);
+  jlong* to = PIN(jlong, Long, text_off);
+  int st = stc_prep_tokens(CTX(ctx), (const stc_prep*)(intptr_t)prep, (const uint8_t*)t, LEN(text), (const int64_t*)to,
+                           LEN(text_off) - 1, &out);
+  UNPIN(Long, text_off, to, JNI_ABORT);
+  UNPIN(Byte, text, t, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+/* {nBytes, nTok, nDocs} */
+JNIEXPORT jlongArray JNICALL FN(tokensShape)(JNIEnv* env, jclass c, jlong tokens) {
+  int64_t s[3] = {0, 0, 0};
+  if (check(env, stc_tokens_shape((const stc_dtok*)(intptr_t)tokens, &s[0], &s[1], &s[2]))) return NULL;
+  jlongArray out = (*env)->NewLongArray(env, 3);
+  if (out) (*env)->SetLongArrayRegion(env, out, 0, 3, (const jlong*)s);
+  return out;
+}
+
+/* every array nullable: utf8Out nBytes, tokOffOut nTok + 1, docOffOut nDocs + 1 */
+JNIEXPORT void JNICALL FN(tokensDownload)(JNIEnv* env, jclass c, jlong ctx, jlong tokens, jbyteArray utf8_out,
+                                          jlongArray tok_off_out, jlongArray doc_off_out) {
+  int64_t s[3] = {0, 0, 0};
+  if (check(env, stc_tokens_shape((const stc_dtok*)(intptr_t)tokens, &s[0], &s[1], &s[2])) ||
+      NEED(utf8_out, s[0], "tokensDownload utf8Out") || NEED(tok_off_out, s[1] + 1, "tokensDownload tokOffOut") ||
+      NEED(doc_off_out, s[2] + 1, "tokensDownload docOffOut"))
+    return;
+  jbyte* u = PIN(jbyte, Byte, utf8_out);
+  jlong* to = PIN(jlong, Long, tok_off_out);
+  jlong* dof = PIN(jlong, Long, doc_off_out);
+  int st = stc_tokens_download(CTX(ctx), (const stc_dtok*)(intptr_t)tokens, (uint8_t*)u, (int64_t*)to, (int64_t*)dof);
+  UNPIN(Long, doc_off_out, dof, 0);
+  UNPIN(Long, tok_off_out, to, 0);
+  UNPIN(Byte, utf8_out, u, 0);
+  check(env, st);
+}
+
+/* the stemmer alone, each token on its own: utf8Out utf8.length, tokOffOut tokOff.length */
+JNIEXPORT void JNICALL FN(stemTokens)(JNIEnv* env, jclass c, jlong ctx, jbyteArray utf8, jlongArray tok_off,
+                                      jbyteArray utf8_out, jlongArray tok_off_out) {
+  if (!tok_off || LEN(tok_off) < 1) {
+    throw_iae(env, "stemTokens: tokOff needs nTok + 1 entries");
+    return;
+  }
+  if (!utf8_out || !tok_off_out) {
+    throw_iae(env, "stemTokens: utf8Out and tokOffOut are required");
+    return;
+  }
+  if (NEED(utf8_out, LEN(utf8), "stemTokens utf8Out") || NEED(tok_off_out, LEN(tok_off), "stemTokens tokOffOut")) return;
+  jbyte* u = PIN(jbyte, Byte, utf8);
+  jlong* to = PIN(jlong, Long, tok_off);
+  jbyte* uo = PIN(jbyte, Byte, utf8_out);
+  jlong* too = PIN(jlong, Long, tok_off_out);
+  int st = stc_stem_tokens(CTX(ctx), (const uint8_t*)u, LEN(utf8), (const int64_t*)to, LEN(tok_off) - 1, (uint8_t*)uo,
+                           (int64_t*)too);
+  UNPIN(Long, tok_off_out, too, 0);
+  UNPIN(Byte, utf8_out, uo, 0);
+  UNPIN(Long, tok_off, to, JNI_ABORT);
+  UNPIN(Byte, utf8, u, JNI_ABORT);
+  check(env, st);
+}
+
 /* ---- one process, N devices (stc_group) ---------------------------------------------------------- */
 /* the same parameters as ldaCreate, plus the device ids */
 JNIEXPORT jlong JNICALL FN(groupCreate)(JNIEnv* env, jclass c, jintArray devices, jint k, jlong vocab,

@@ -142,6 +142,19 @@ public final class StcNative {
                                               int valueDtype);
   public static native void cvFree(long model);
 
+  /** the reference's text preprocessing behind its lemmatiser (stc_prep_*: strip, SimpleTokenizer, stop words,
+   *  Porter stemmer); stripCp null = the reference's set, stop word j = stopUtf8[stopOff[j], stopOff[j+1]) */
+  public static native long prepCreate(long ctx, int[] stripCp, byte[] stopUtf8, long[] stopOff, boolean stem);
+  public static native void prepFree(long prep);
+  /** document d = text[textOff[d], textOff[d+1]); the result is device tokens (tokensFree) */
+  public static native long prepTokens(long ctx, long prep, byte[] text, long[] textOff);
+  /** {nBytes, nTok, nDocs} of device tokens */
+  public static native long[] tokensShape(long tokens);
+  /** every array nullable: utf8Out nBytes, tokOffOut nTok + 1, docOffOut nDocs + 1 */
+  public static native void tokensDownload(long ctx, long tokens, byte[] utf8Out, long[] tokOffOut, long[] docOffOut);
+  /** the stemmer alone, each token on its own: utf8Out utf8.length, tokOffOut tokOff.length */
+  public static native void stemTokens(long ctx, byte[] utf8, long[] tokOff, byte[] utf8Out, long[] tokOffOut);
+
   // ---- host helpers (pure Java): Spark vectors → CSR arrays
   /** CSR of sparse or dense rows: {indptr long[n+1], indices int[nnz], values double[nnz]} */
   public static Object[] toCsr(org.apache.spark.mllib.linalg.Vector[] rows) {

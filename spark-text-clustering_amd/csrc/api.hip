@@ -22,6 +22,7 @@
 #include "count_vectorizer.h"
 #include "lda_em.h"
 #include "lda_kernels.h"
+#include "stc_handles.h"
 
 namespace stc {
 
@@ -32,20 +33,10 @@ void set_last_error(const std::string& msg) { g_last_error = msg; }
 
 using namespace stc;
 
-struct stc_ctx : Ctx {};
-
 // the contexts that exist (stc_dcsr_free hands a matrix's buffers back only to a live one)
 static std::mutex g_live_mu;
 static std::unordered_set<stc_ctx*> g_live;
 struct stc_dcsr : DCsr {};
-struct stc_dtok {
-  Ctx* ctx = nullptr;  // the context it was uploaded on; only it may read the buffers
-  int device = -1;     // for stc_tokens_free, which may run after that context is gone
-  DevBuf utf8, tok_off, doc_off;
-  int64_t n_bytes = 0, n_tok = 0, n_docs = 0;
-  int64_t max_doc = -1;  // the longest document's token count (from the upload's offsets)
-  bool off32 = false;    // tok_off holds u32 offsets (blob + padding < 4 GiB), else int64
-};
 
 // ---------------------------------------------------------------------------------------
 // LDA state

@@ -1,4 +1,4 @@
-"""stc — MI355X-native HashingTF / CountVectorizer → IDF → LDA (online and EM) hot path of borisfoko/Spark-Text-Clustering.
+"""stc — MI355X-native text preprocessing → HashingTF / CountVectorizer → IDF → LDA (online and EM) hot path of borisfoko/Spark-Text-Clustering.
 
 The compute lives in libstc.so (HIP kernels for gfx950 behind the C ABI in include/stc.h); this
 package is the host-side mirror of the Spark ML interface the reference's pipeline uses.
@@ -12,9 +12,10 @@ from .clustering import (LDA, ML_LDA_DEFAULT_SEED, DistributedLDAModel, EmHandle
 from .core import Context, CsrMatrix, DeviceCsr
 from .count_vectorizer import CountVectorizer, CountVectorizerModel
 from .feature import IDF, DeviceTokens, HashingTF, IDFModel, Tokenizer, encode_texts, encode_tokens
+from .text_prep import DEFAULT_STRIP_CHARS, PorterStemmer, TextPreprocessor
 
 __all__ = [
-    "Context", "CsrMatrix", "DeviceCsr", "CountVectorizer", "CountVectorizerModel", "HashingTF", "IDF", "IDFModel", "Tokenizer", "encode_texts", "encode_tokens", "LDA",
+    "Context", "CsrMatrix", "DeviceCsr", "CountVectorizer", "CountVectorizerModel", "HashingTF", "IDF", "IDFModel", "Tokenizer", "DeviceTokens", "TextPreprocessor", "PorterStemmer", "DEFAULT_STRIP_CHARS", "encode_texts", "encode_tokens", "LDA",
     "LDAModel", "DistributedLDAModel", "LdaGroup", "LdaHandle", "EmHandle", "io", "MllibLDA", "OnlineLDAOptimizer",
     "EMLDAOptimizer", "em_concentrations", "ML_LDA_DEFAULT_SEED", "reference_mini_batch_fraction", "StcError", "StcIllegalArgument", "load", "STC_F32", "STC_F64", "STC_MIXED",
     "STC_HASH_STANDARD", "STC_HASH_SPARK24", "STC_LAYOUT_VK", "STC_LAYOUT_KV", "STC_ERR_INVALID_ARG", "STC_ERR_HIP",

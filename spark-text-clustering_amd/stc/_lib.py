@@ -33,6 +33,7 @@ _pi32 = C.POINTER(C.c_int32)
 _pi64 = C.POINTER(C.c_int64)
 _pdbl = C.POINTER(C.c_double)
 _pu8 = C.POINTER(C.c_uint8)
+_pu32 = C.POINTER(C.c_uint32)
 
 
 class LdaConfig(C.Structure):
@@ -102,6 +103,12 @@ SIGNATURES = {
     "stc_cv_transform_dev": (_int, [_p, _p, _pu8, _i64, _pi64, _i64, _pi64, _i64, _dbl, _int, _int, C.POINTER(_p)]),
     "stc_cv_transform_tokens": (_int, [_p, _p, _p, _dbl, _int, _int, C.POINTER(_p)]),
     "stc_cv_free": (_int, [_p]),
+    "stc_prep_create": (_int, [_p, _pu32, _i64, _pu8, _i64, _pi64, _i64, _int, C.POINTER(_p)]),
+    "stc_prep_free": (_int, [_p]),
+    "stc_prep_tokens": (_int, [_p, _p, _pu8, _i64, _pi64, _i64, C.POINTER(_p)]),
+    "stc_tokens_shape": (_int, [_p, _pi64, _pi64, _pi64]),
+    "stc_tokens_download": (_int, [_p, _p, _pu8, _pi64, _pi64]),
+    "stc_stem_tokens": (_int, [_p, _pu8, _i64, _pi64, _i64, _pu8, _pi64]),
     "stc_tokenize": (_int, [_p, _pu8, _i64, _pi64, _i64, _pu8, _i64, _pi64, _pi64, _pi64, _pi64]),
     "stc_tokenize_hashing_tf_dev": (_int, [_p, _pu8, _i64, _pi64, _i64, _i32, _int, _int, _int,
                                            C.POINTER(_p)]),

@@ -57,6 +57,25 @@ class DeviceTokens:
         self.ctx, self.handle = ctx, h
         self.n_bytes, self.n_tok, self.n_docs = blob.size, tok_off.size - 1, doc_off.size - 1
 
+    @classmethod
+    def from_handle(cls, ctx: Context, handle):
+        """Wraps an stc_dtok the library made (TextPreprocessor.transform_device); the object owns it."""
+        self = cls.__new__(cls)
+        nb, nt, nd = C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(ctx.lib.stc_tokens_shape(handle, C.byref(nb), C.byref(nt), C.byref(nd)))
+        self.ctx, self.handle = ctx, handle
+        self.n_bytes, self.n_tok, self.n_docs = nb.value, nt.value, nd.value
+        return self
+
+    def download(self):
+        """the (utf8 uint8 blob, tok_off int64[n_tok+1], doc_off int64[n_docs+1]) triple, copied to the host"""
+        blob = np.zeros(max(self.n_bytes, 1), np.uint8)
+        tok_off = np.zeros(self.n_tok + 1, np.int64)
+        doc_off = np.zeros(self.n_docs + 1, np.int64)
+        L.check(self.ctx.lib.stc_tokens_download(self.ctx.handle, self.handle, L.ptr(blob, C.c_uint8),
+                                                 L.ptr(tok_off, C.c_int64), L.ptr(doc_off, C.c_int64)))
+        return blob[:self.n_bytes], tok_off, doc_off
+
     def free(self):
         if self.handle:
             self.ctx.lib.stc_tokens_free(self.handle)

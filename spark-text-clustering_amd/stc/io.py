@@ -256,6 +256,20 @@ def save_vocabulary(path, terms):
         f.write(",".join(terms))
 
 
+def load_stop_words(path):
+    """The reference's stop-word file (resources/stopWords_*.txt) as LDAClustering.scala:128 reads it: every line
+    split on ``,`` (Java's ``split`` drops trailing empty strings), all lines concatenated."""
+    with open(path, encoding="utf-8", newline="") as f:
+        text = f.read()
+    words = []
+    for line in text.splitlines():
+        parts = line.split(",")
+        while parts and parts[-1] == "":
+            parts.pop()
+        words.extend(parts)
+    return words
+
+
 def load_vocabulary(path):
     """Reads it as LDALoader.scala:43 does: the first line, ``split(",")`` (Java drops trailing empty strings)."""
     with open(path, encoding="utf-8", newline="") as f:
