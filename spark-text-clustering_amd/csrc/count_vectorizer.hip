@@ -25,11 +25,38 @@
 #include <cstdlib>
 #include <memory>
 
-#include "count_vectorizer.h"
+#include "collectives.h"
+#include "stc_handles.h"
+
+// CountVectorizerModel: term j is blob[term_off[j] .. term_off[j+1]), index = position
+struct stc_cvm {
+  stc::Ctx* ctx = nullptr;  // the context that made it; only it may read the buffers (checked at the ABI)
+  int device = -1;          // for stc_cv_free, which may run after that context is gone
+  int64_t n_terms = 0, n_bytes = 0;
+  int hash_bits = 64;       // STC_CV_HASH_BITS at construction: the hash is masked to its low bits everywhere
+  bool has_counts = false;  // fitted (count / df hold the corpus statistics) or made from a list (zeros)
+  uint64_t table_mask = 0;  // table slots − 1 (a power of two ≥ 2 · n_terms: load ≤ 0.5)
+  stc::DevBuf blob;         // uint8[n_bytes + kHashPad]
+  stc::DevBuf term_off;     // int64[n_terms + 1]
+  stc::DevBuf count, df;    // int64[n_terms]
+  stc::DevBuf table;        // Slot[table_mask + 1]: term index (−1 = empty), length, first 16 bytes, blob offset
+};
 
 namespace stc {
 namespace cv {
 namespace {
+
+// tokens on the device: token t is utf8[off[t] .. off[t+1]) with off = off32 when given, else off64; the
+// blob carries kHashPad bytes of padding; document d owns tokens [doc_off[d], doc_off[d+1])
+struct TokView {
+  const uint8_t* utf8 = nullptr;
+  const int64_t* off64 = nullptr;
+  const uint32_t* off32 = nullptr;
+  int64_t n_tok = 0;
+  const int64_t* doc_off = nullptr;  // nullptr for index_of
+  int64_t n_docs = 0;
+  int64_t max_doc = -1;  // the longest document's token count when the upload knows it, −1 otherwise
+};
 
 // ---------------------------------------------------------------------------------------
 // strings: read as whole aligned dwords and realigned with v_alignbyte (as hashing_tf.hip's k_hash);
@@ -381,9 +408,7 @@ int32_t build_table(Ctx& c, stc_cvm& m) {
 }
 
 std::unique_ptr<stc_cvm> new_model(Ctx& c) {
-  auto m = std::make_unique<stc_cvm>();
-  m->ctx = &c;
-  m->device = c.device;
+  auto m = new_handle<stc_cvm>(c);
   m->hash_bits = hash_bits_env();
   return m;
 }
@@ -558,10 +583,8 @@ __global__ __launch_bounds__(256) void k_tf_emit(const int32_t* __restrict__ key
     }
 }
 
-}  // namespace
-
 // ---------------------------------------------------------------------------------------
-// entry points
+// the model's operations, behind the stc_cv_* entry points below
 // ---------------------------------------------------------------------------------------
 stc_cvm* fit(Ctx& c, const TokView& tk, int64_t vocab_size, double min_df, double max_df) {
   single_device(c);
@@ -596,12 +619,9 @@ stc_cvm* fit(Ctx& c, const TokView& tk, int64_t vocab_size, double min_df, doubl
 
   with_off(tk, [&](const auto* off) { k_cv_hash<<<grid_for(n), 256, 0, st>>>(tk.utf8, off, n, mask, hk, ti); });
   KERNEL_CHECK();
-  {
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, hk, hk2, ti, ti2, (int)n, 0, m->hash_bits, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, hk, hk2, ti, ti2, (int)n, 0, m->hash_bits, st));
-  }
+  with_temp(tmp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortPairs(t, tb, hk, hk2, ti, ti2, (int)n, 0, m->hash_bits, st);
+  });
   auto heads = [&] {
     with_off(tk, [&](const auto* off) {
       k_cv_heads<<<grid_for(n), 256, 0, st>>>(tk.utf8, off, tk.doc_off, tk.n_docs, hk2, ti2, n, fl, small);
@@ -620,21 +640,16 @@ stc_cvm* fit(Ctx& c, const TokView& tk, int64_t vocab_size, double min_df, doubl
     with_off(tk, [&](const auto* off) {
       using O = std::remove_cv_t<std::remove_pointer_t<decltype(off)>>;
       HashTokLess<O> less{tk.utf8, off};
-      size_t tb = 0;
-      HIP_CHECK(hipcub::DeviceMergeSort::SortKeys(nullptr, tb, pk.as<HashTok>(), (int)n, less, st));
-      tmp.reserve(tb);
-      HIP_CHECK(hipcub::DeviceMergeSort::SortKeys(tmp.p, tb, pk.as<HashTok>(), (int)n, less, st));
+      with_temp(tmp, [&](void* t, size_t& tb) {
+        return hipcub::DeviceMergeSort::SortKeys(t, tb, pk.as<HashTok>(), (int)n, less, st);
+      });
     });
     k_cv_unpack<<<grid_for(n), 256, 0, st>>>(pk.as<HashTok>(), n, hk2, ti2);
     KERNEL_CHECK();
     heads();
   }
-  {  // inclusive scan of (heads << 32 | document flags), in place
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, fl, fl, (int)n, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, fl, fl, (int)n, st));
-  }
+  // inclusive scan of (heads << 32 | document flags), in place
+  with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, fl, fl, (int)n, st); });
   int64_t last = 0;
   HIP_CHECK(hipMemcpyAsync(&last, fl + (n - 1), 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
@@ -655,10 +670,9 @@ stc_cvm* fit(Ctx& c, const TokView& tk, int64_t vocab_size, double min_df, doubl
     using O = std::remove_cv_t<std::remove_pointer_t<decltype(off)>>;
     k_cv_keys<<<grid_for(U), 256, 0, st>>>(tk.utf8, off, ti2, start, dstart, U, min_cnt, max_cnt, keys, ids, small + 1);
     TermLess<O> less{tk.utf8, off};
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceMergeSort::SortPairs(nullptr, tb, keys, ids, (int)U, less, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceMergeSort::SortPairs(tmp.p, tb, keys, ids, (int)U, less, st));
+    with_temp(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceMergeSort::SortPairs(t, tb, keys, ids, (int)U, less, st);
+    });
   });
   KERNEL_CHECK();
   int32_t kept = 0;
@@ -678,12 +692,9 @@ stc_cvm* fit(Ctx& c, const TokView& tk, int64_t vocab_size, double min_df, doubl
   });
   KERNEL_CHECK();
   HIP_CHECK(hipMemsetAsync(term_off, 0, 8, st));
-  {
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, len, term_off + 1, (int)n_keep, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, len, term_off + 1, (int)n_keep, st));
-  }
+  with_temp(tmp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceScan::InclusiveSum(t, tb, len, term_off + 1, (int)n_keep, st);
+  });
   HIP_CHECK(hipMemcpyAsync(&m->n_bytes, term_off + n_keep, 8, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
   m->blob.reserve(m->n_bytes + kHashPad);
@@ -699,8 +710,7 @@ stc_cvm* from_vocabulary(Ctx& c, const uint8_t* utf8, int64_t n_bytes, const int
   single_device(c);
   STC_REQUIRE(n_terms > 0 && n_terms < (int64_t(1) << 31), "the vocabulary must hold 1..2^31-1 terms");
   STC_REQUIRE(n_bytes >= 0 && term_off && (n_bytes == 0 || utf8), "utf8/term_off");
-  STC_REQUIRE(term_off[0] == 0 && term_off[n_terms] <= n_bytes, "term_off must start at 0 and stay within n_bytes");
-  for (int64_t j = 0; j < n_terms; ++j) STC_REQUIRE(term_off[j + 1] >= term_off[j], "term_off must be non-decreasing");
+  check_offsets("term_off", term_off, n_terms, n_bytes, "n_bytes", false);
   c.use();
   auto m = new_model(c);
   hipStream_t st = c.stream;
@@ -793,22 +803,16 @@ void transform(Ctx& c, const stc_cvm& m, const TokView& tk, double min_tf, int b
     KERNEL_CHECK();
     int nbits = 1;
     while ((int64_t(1) << nbits) <= m.n_terms) ++nbits;
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb, k, k2, (int)n, n_large, beg, end, 0, nbits, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, tb, k, k2, (int)n, n_large, beg, end, 0, nbits, st));
+    with_temp(tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceSegmentedRadixSort::SortKeys(t, tb, k, k2, (int)n, n_large, beg, end, 0, nbits, st);
+    });
   }
   HIP_CHECK(hipMemsetAsync(rid, 0, 4 * n, st));
   k_tf_doc_starts<<<grid_for(n_docs), 256, 0, st>>>(tk.doc_off, n_docs, rid);
   KERNEL_CHECK();
   k_tf_heads<<<grid_for(n), 256, 0, st>>>(k2, n, rid);
   KERNEL_CHECK();
-  {
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, rid, rid, (int)n, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, rid, rid, (int)n, st));
-  }
+  with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, rid, rid, (int)n, st); });
   int32_t n_runs = 0;
   HIP_CHECK(hipMemcpyAsync(&n_runs, rid + (n - 1), 4, hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));
@@ -824,12 +828,7 @@ void transform(Ctx& c, const stc_cvm& m, const TokView& tk, double min_tf, int b
   KERNEL_CHECK();
   k_tf_keep<<<grid_for(n_runs + 1), 256, 0, st>>>(k2, rstart, n_runs, tk.doc_off, n_docs, oov, min_tf, keep);
   KERNEL_CHECK();
-  {
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, keep, slot, n_runs + 1, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, keep, slot, n_runs + 1, st));
-  }
+  with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, keep, slot, n_runs + 1, st); });
   k_tf_indptr<<<grid_for(n_docs + 1), 256, 0, st>>>(tk.doc_off, n_docs, rid, slot, out.indptr.as<int64_t>());
   KERNEL_CHECK();
   int32_t total = 0;
@@ -856,5 +855,138 @@ void destroy(stc_cvm* m) {
   delete m;
 }
 
+void cv_view_upload(const TokenUpload& u, int64_t n_tok, int64_t n_docs, TokView& v) {
+  v.utf8 = u.utf8.as<uint8_t>();
+  v.off64 = u.tok_off.as<int64_t>();
+  v.n_tok = n_tok;
+  v.doc_off = u.doc_off.as<int64_t>();
+  v.n_docs = n_docs;
+  v.max_doc = u.max_doc;
+}
+void cv_view_tokens(const stc_dtok& t, TokView& v) {
+  v.utf8 = t.utf8.as<uint8_t>();
+  if (t.off32) v.off32 = t.tok_off.as<uint32_t>();
+  else v.off64 = t.tok_off.as<int64_t>();
+  v.n_tok = t.n_tok;
+  v.doc_off = t.doc_off.as<int64_t>();
+  v.n_docs = t.n_docs;
+  v.max_doc = t.max_doc;
+}
+
+}  // namespace
 }  // namespace cv
 }  // namespace stc
+
+using namespace stc;
+
+extern "C" {
+
+// ---- C ABI: the pointers are checked and host tokens uploaded (padded as stc_tokens_upload does) here ----
+
+int stc_cv_fit(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off, int64_t n_tok,
+               const int64_t* doc_off, int64_t n_docs, int64_t vocab_size, double min_df, double max_df,
+               stc_cvm** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && doc_off && out, "ctx/doc_off/out");
+    ctx->use();
+    TokenUpload u;
+    upload_tokens(*ctx, u, utf8, n_bytes, tok_off, n_tok, doc_off, n_docs);
+    wait_stream(*ctx, ctx->stream);
+    cv::TokView v;
+    cv::cv_view_upload(u, n_tok, n_docs, v);
+    *out = cv::fit(*ctx, v, vocab_size, min_df, max_df);
+  });
+}
+
+int stc_cv_fit_tokens(stc_ctx* ctx, const stc_dtok* tokens, int64_t vocab_size, double min_df, double max_df,
+                      stc_cvm** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && tokens && out, "ctx/tokens/out");
+    STC_REQUIRE(tokens->ctx == ctx, "tokens were uploaded on another stc_ctx");
+    cv::TokView v;
+    cv::cv_view_tokens(*tokens, v);
+    *out = cv::fit(*ctx, v, vocab_size, min_df, max_df);
+  });
+}
+
+int stc_cv_from_vocabulary(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* term_off,
+                           int64_t n_terms, stc_cvm** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && out, "ctx/out");
+    *out = cv::from_vocabulary(*ctx, utf8, n_bytes, term_off, n_terms);
+  });
+}
+
+int stc_cv_shape(const stc_cvm* model, int64_t* n_terms_out, int64_t* n_bytes_out) {
+  return guard([&] {
+    STC_REQUIRE(model, "model");
+    if (n_terms_out) *n_terms_out = model->n_terms;
+    if (n_bytes_out) *n_bytes_out = model->n_bytes;
+  });
+}
+
+int stc_cv_get(stc_ctx* ctx, const stc_cvm* model, uint8_t* utf8_out, int64_t* term_off_out, int64_t* count_out,
+               int64_t* df_out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model, "ctx/model");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    cv::get(*ctx, *model, utf8_out, term_off_out, count_out, df_out);
+  });
+}
+
+int stc_cv_index_of(stc_ctx* ctx, const stc_cvm* model, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off,
+                    int64_t n_tok, int32_t* idx_out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model && (idx_out || n_tok == 0), "ctx/model/idx_out");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    ctx->use();
+    TokenUpload u;
+    upload_tokens(*ctx, u, utf8, n_bytes, tok_off, n_tok, nullptr, 0);
+    wait_stream(*ctx, ctx->stream);
+    cv::TokView v;
+    cv::cv_view_upload(u, n_tok, 0, v);
+    v.doc_off = nullptr;
+    cv::index_of(*ctx, *model, v, idx_out);
+  });
+}
+
+int stc_cv_transform_dev(stc_ctx* ctx, const stc_cvm* model, const uint8_t* utf8, int64_t n_bytes,
+                         const int64_t* tok_off, int64_t n_tok, const int64_t* doc_off, int64_t n_docs, double min_tf,
+                         int binary, int value_dtype, stc_dcsr** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model && doc_off && out, "ctx/model/doc_off/out");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    STC_REQUIRE(value_dtype == STC_F32 || value_dtype == STC_F64, "value_dtype");
+    ctx->use();
+    TokenUpload u;
+    upload_tokens(*ctx, u, utf8, n_bytes, tok_off, n_tok, doc_off, n_docs);
+    wait_stream(*ctx, ctx->stream);
+    auto m = new_handle<stc_dcsr>(*ctx);
+    cv::TokView v;
+    cv::cv_view_upload(u, n_tok, n_docs, v);
+    cv::transform(*ctx, *model, v, min_tf, binary, value_dtype, *m);
+    wait_stream(*ctx, ctx->stream);  // the uploaded tokens are freed on return
+    *out = m.release();
+  });
+}
+
+int stc_cv_transform_tokens(stc_ctx* ctx, const stc_cvm* model, const stc_dtok* tokens, double min_tf, int binary,
+                            int value_dtype, stc_dcsr** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && model && tokens && out, "ctx/model/tokens/out");
+    STC_REQUIRE(model->ctx == ctx, "the model belongs to another stc_ctx");
+    STC_REQUIRE(tokens->ctx == ctx, "tokens were uploaded on another stc_ctx");
+    STC_REQUIRE(value_dtype == STC_F32 || value_dtype == STC_F64, "value_dtype");
+    auto m = new_handle<stc_dcsr>(*ctx);
+    cv::TokView v;
+    cv::cv_view_tokens(*tokens, v);
+    cv::transform(*ctx, *model, v, min_tf, binary, value_dtype, *m);
+    *out = m.release();
+  });
+}
+
+int stc_cv_free(stc_cvm* model) {
+  return guard([&] { cv::destroy(model); });
+}
+
+}  // extern "C"

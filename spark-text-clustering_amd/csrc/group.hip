@@ -1,0 +1,466 @@
+// group.hip — stc_group: one process driving N devices (stc_init(device_ids, n)).  The JVM runs the
+// reference in ONE process (Spark local[*], LDATraining.scala:7), so its drop-in needs the N GPUs of the node behind
+// one handle: N contexts joined by one communicator (ncclCommInitAll over distinct devices; the in-process transport
+// of collectives.h when every member shares one device), N LDA handles over contiguous document shards (balanced by
+// entries), each call run on one host thread per member.  Built on the public ABI, collectives.h and the member
+// accessors of lda_online.h.
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <exception>
+#include <memory>
+#include <thread>
+
+#include "collectives.h"
+#include "lda_online.h"
+#include "stc_handles.h"
+
+using namespace stc;
+
+struct stc_group {
+  std::vector<stc_ctx*> ctx;
+  std::vector<stc_lda*> lda;
+  std::vector<stc_dcsr*> shard;
+  std::vector<int64_t> row0;  // first corpus row of each member's shard (n + 1 entries)
+  std::unique_ptr<LocalColl> local;
+  int64_t rows = 0, cols = 0, k = 0;  // the corpus's shape; the members' topic count
+  int dtype = STC_F64;
+  int transport = STC_TRANSPORT_NONE;  // how the members' collectives travel (stc_group_transport)
+  bool threaded = false;               // run even a one-member call on its own host thread (STC_GROUP_RCCL)
+  // RCCL fault handling: a member's failure sets `abort` (every member's waits then throw instead of waiting
+  // on collectives the failed member never joins) and, after the call, aborts every member's communicator;
+  // the group is then `broken`: every later call but destroy fails with STC_ERR_STATE
+  std::atomic<bool> abort{false};
+  bool broken = false;
+  std::string broken_why;
+  int n() const { return (int)ctx.size(); }
+};
+
+namespace {
+
+void member_ok(int rc) {
+  if (rc != STC_OK) throw Error(rc, stc_last_error());
+}
+void require_usable(const stc_group& g) {
+  if (g.broken) throw Error(STC_ERR_STATE, "the group's RCCL communicator was aborted after a member failed (" +
+                                               g.broken_why + "): destroy the group and create a new one");
+}
+// f(i) for every member on its own thread (device set); the first failure is rethrown here.
+// In-process transport: a failure releases the members waiting in its barrier, and the group stays usable.
+// RCCL: a failure sets the group's abort flag, so every member's next wait throws instead of waiting for a
+// collective the failed member never enqueued; a member still blocked inside the runtime after a grace
+// period (a copy queued behind such a collective) has its communicator aborted by this thread, which
+// releases the collective's kernels; after the join every member's communicator is aborted and the group
+// is broken (STC_ERR_STATE from then on; stc_group_destroy returns).
+template <typename F>
+void for_members(stc_group& g, F f) {
+  require_usable(g);
+  const int n = g.n();
+  const bool rccl = g.transport == STC_TRANSPORT_RCCL;
+  std::vector<std::exception_ptr> err((size_t)n);
+  std::mutex fm;
+  std::condition_variable fcv;
+  int first = -1;  // the member that failed first (the others may only report "another member failed")
+  int running = n;
+  auto run = [&](int i) {
+    try {
+      g.ctx[(size_t)i]->use();
+      f(i);
+    } catch (...) {
+      err[(size_t)i] = std::current_exception();
+      {
+        std::lock_guard<std::mutex> lk(fm);
+        if (first < 0) first = i;
+      }
+      if (g.local) g.local->fail();  // release the members waiting in a barrier
+      if (rccl) g.abort.store(true);
+    }
+    std::lock_guard<std::mutex> lk(fm);
+    --running;
+    fcv.notify_all();
+  };
+  if (n == 1 && !g.threaded) {
+    run(0);
+  } else {
+    std::vector<std::thread> th;
+    th.reserve((size_t)n);
+    for (int i = 0; i < n; ++i) th.emplace_back(run, i);
+    if (rccl) {
+      std::unique_lock<std::mutex> lk(fm);
+      fcv.wait(lk, [&] { return running == 0 || first >= 0; });
+      if (running > 0 && !fcv.wait_for(lk, std::chrono::seconds(5), [&] { return running == 0; }))
+        for (auto* c : g.ctx) abort_comm(*c);  // members still blocked behind the failed member's collectives
+    }
+    for (auto& t : th) t.join();
+  }
+  if (g.local) {  // a failed call leaves the transport usable for the next one
+    std::lock_guard<std::mutex> lk(g.local->m);
+    g.local->broken = false;
+    g.local->arrived = 0;
+  }
+  if (first >= 0) {
+    if (rccl) {
+      for (auto* c : g.ctx) {
+        c->use();
+        abort_comm(*c);
+      }
+      g.broken = true;
+      try {
+        std::rethrow_exception(err[(size_t)first]);
+      } catch (const std::exception& e) {
+        g.broken_why = "member " + std::to_string(first) + ": " + e.what();
+      } catch (...) {
+        g.broken_why = "member " + std::to_string(first);
+      }
+    }
+    std::rethrow_exception(err[(size_t)first]);
+  }
+}
+// contiguous row ranges of a host CSR, one per member, balanced by entries
+std::vector<int64_t> shard_rows(const int64_t* indptr, int64_t rows, int n) {
+  std::vector<int64_t> r0((size_t)n + 1, rows);
+  r0[0] = 0;
+  const int64_t nnz = indptr[rows];
+  int64_t r = 0;
+  for (int q = 1; q < n; ++q) {
+    const int64_t target = (nnz * q + n - 1) / n;
+    while (r < rows && indptr[r] < target) ++r;
+    r0[(size_t)q] = std::max(r, r0[(size_t)q - 1]);
+  }
+  return r0;
+}
+// member i's rows [r0[i], r0[i+1]) of a host CSR uploaded to its device (indptr rebased)
+stc_dcsr* upload_rows(stc_ctx* ctx, int64_t lo, int64_t hi, int64_t cols, const int64_t* indptr,
+                      const int32_t* indices, const double* values, int dtype) {
+  std::vector<int64_t> ip((size_t)(hi - lo + 1));
+  for (int64_t r = lo; r <= hi; ++r) ip[(size_t)(r - lo)] = indptr[r] - indptr[lo];
+  stc_dcsr* d = nullptr;
+  member_ok(stc_dcsr_upload(ctx, hi - lo, cols, ip.data(), indices ? indices + indptr[lo] : nullptr,
+                            values ? values + indptr[lo] : nullptr, dtype, &d));
+  return d;
+}
+
+}  // namespace
+
+extern "C" {
+
+int stc_group_create(const int* device_ids, int n_devices, const stc_lda_config* cfg, stc_group** out) {
+  return guard([&] {
+    STC_REQUIRE(device_ids && cfg && out, "device_ids/cfg/out");
+    STC_REQUIRE(n_devices >= 1 && n_devices <= kMaxMembers, "1 <= n_devices <= 16");
+    int nd = 0;
+    HIP_CHECK(hipGetDeviceCount(&nd));
+    bool same = true, distinct = true;
+    for (int i = 0; i < n_devices; ++i) {
+      STC_REQUIRE(device_ids[i] >= 0 && device_ids[i] < nd, "device index out of range");
+      same &= device_ids[i] == device_ids[0];
+      for (int j = 0; j < i; ++j) distinct &= device_ids[i] != device_ids[j];
+    }
+    STC_REQUIRE(same || distinct, "device_ids: all distinct (RCCL) or all the same device (in-process)");
+    auto g = std::make_unique<stc_group>();
+    struct Cleanup {
+      stc_group* g;
+      ~Cleanup() {
+        if (!g) return;
+        for (auto* l : g->lda) (void)stc_lda_destroy(l);
+        for (auto* c : g->ctx) (void)stc_destroy(c);
+      }
+    } cleanup{g.get()};
+    for (int i = 0; i < n_devices; ++i) {
+      stc_ctx* c = nullptr;
+      member_ok(stc_init(device_ids[i], &c));
+      g->ctx.push_back(c);
+    }
+    // debug knob STC_GROUP_RCCL=1: a group of distinct devices — one device included — builds its RCCL
+    // communicator with ncclCommInitAll, runs the collective (vocabulary-sliced) M-step even with one member,
+    // and drives every member from its own host thread: the configs[2] drop-in path (one JVM, N GPUs,
+    // LDATraining.scala:7) exercised end to end on a one-GPU box, where no two-device communicator exists
+    const char* gr = getenv("STC_GROUP_RCCL");
+    const bool rccl1 = gr && gr[0] == '1' && distinct;
+    if (n_devices > 1 && same) {
+      g->local = std::make_unique<LocalColl>(n_devices);
+      g->transport = STC_TRANSPORT_IN_PROCESS;
+    }
+    if (n_devices > 1 || rccl1) {
+      std::vector<ncclComm_t> comms((size_t)n_devices, nullptr);
+      if (!g->local) {
+        RCCL_CHECK(ncclCommInitAll(comms.data(), n_devices, device_ids));
+        g->transport = STC_TRANSPORT_RCCL;
+      }
+      g->threaded = rccl1;
+      for (int i = 0; i < n_devices; ++i) {
+        g->ctx[(size_t)i]->comm = comms[(size_t)i];
+        g->ctx[(size_t)i]->local = g->local.get();
+        g->ctx[(size_t)i]->n_ranks = n_devices;
+        g->ctx[(size_t)i]->rank = i;
+      }
+    }
+    for (auto* c : g->ctx) c->abort_flag = &g->abort;
+    // test knob STC_GROUP_STEP_FAULT=i[:s]: member i's s-th step (default the first) fails, after its E-step
+    // and sstats and before its reduce-scatter (its peers' collectives then never complete: the RCCL
+    // failure path)
+    const char* sf = getenv("STC_GROUP_STEP_FAULT");
+    const int step_fault = sf && sf[0] ? atoi(sf) : -1;
+    const char* sfc = sf ? std::strchr(sf, ':') : nullptr;
+    const int step_fault_at = sfc ? std::max(1, atoi(sfc + 1)) : 1;
+    for (int i = 0; i < n_devices; ++i) {
+      stc_lda* l = nullptr;
+      member_ok(stc_lda_create(g->ctx[(size_t)i], cfg, &l));
+      // rccl1: the sliced M-step and its collectives on a 1-rank communicator too
+      set_group_knobs(*l, rccl1, i == step_fault ? step_fault_at : 0);
+      g->lda.push_back(l);
+    }
+    g->dtype = corpus_dtype(*g->lda[0]);  // the shards' value dtype
+    g->k = cfg->k;
+    g->row0.assign((size_t)n_devices + 1, 0);
+    cleanup.g = nullptr;
+    *out = g.release();
+  });
+}
+
+int stc_group_destroy(stc_group* g) {
+  return guard([&] {
+    if (!g) return;
+    for (auto* l : g->lda) (void)stc_lda_destroy(l);
+    for (auto* d : g->shard) (void)stc_dcsr_free(d);
+    for (auto* c : g->ctx) {
+      c->local = nullptr;
+      (void)stc_destroy(c);
+    }
+    delete g;
+  });
+}
+
+int stc_group_size(const stc_group* g, int* n_out) {
+  return guard([&] {
+    STC_REQUIRE(g && n_out, "group/n_out");
+    *n_out = g->n();
+  });
+}
+
+int stc_group_transport(const stc_group* g, int* transport_out) {
+  return guard([&] {
+    STC_REQUIRE(g && transport_out, "group/transport_out");
+    *transport_out = g->transport;
+  });
+}
+
+int stc_group_member(stc_group* g, int i, stc_lda** lda_out) {
+  return guard([&] {
+    STC_REQUIRE(g && lda_out && i >= 0 && i < g->n(), "group/member index");
+    *lda_out = g->lda[(size_t)i];
+  });
+}
+
+int stc_group_set_corpus(stc_group* g, int64_t n_rows, int64_t n_cols, const int64_t* indptr, const int32_t* indices,
+                         const double* values) {
+  return guard([&] {
+    STC_REQUIRE(g, "group");
+    check_host_csr(n_rows, n_cols, indptr, indices, values);
+    const std::vector<int64_t> r0 = shard_rows(indptr, n_rows, g->n());
+    std::vector<stc_dcsr*> shard((size_t)g->n(), nullptr);
+    try {
+      // every shard uploaded before any member is switched to it: a failed upload (out of memory) leaves
+      // every member on its previous shard
+      const char* fe = getenv("STC_GROUP_UPLOAD_FAULT");  // debug knob: member i's upload fails (tests)
+      const int fault = fe ? atoi(fe) : -1;
+      for_members(*g, [&](int i) {
+        if (i == fault) throw Error(STC_ERR_OOM, "injected shard upload failure (STC_GROUP_UPLOAD_FAULT)");
+        shard[(size_t)i] = upload_rows(g->ctx[(size_t)i], r0[(size_t)i], r0[(size_t)i + 1], n_cols, indptr, indices,
+                                       values, g->dtype);
+      });
+      for_members(*g, [&](int i) { member_ok(stc_lda_set_corpus(g->lda[(size_t)i], shard[(size_t)i], n_rows)); });
+    } catch (...) {
+      // members already switched go back to their previous shard (or to none) before the new ones are freed
+      for (int i = 0; i < g->n(); ++i) {
+        stc_lda* l = g->lda[(size_t)i];
+        if (!shard[(size_t)i] || corpus(*l) != shard[(size_t)i]) continue;
+        stc_dcsr* old = (size_t)i < g->shard.size() ? g->shard[(size_t)i] : nullptr;
+        if (!old || stc_lda_set_corpus(l, old, g->rows) != STC_OK) forget_corpus(*l);
+      }
+      for (auto* d : shard) (void)stc_dcsr_free(d);
+      throw;
+    }
+    for (auto* d : g->shard) (void)stc_dcsr_free(d);
+    g->shard = shard;
+    g->row0 = r0;
+    g->rows = n_rows;
+    g->cols = n_cols;
+  });
+}
+
+int stc_group_release_corpus(stc_group* g) {
+  return guard([&] {
+    STC_REQUIRE(g, "group");
+    require_usable(*g);
+    for (int i = 0; i < g->n(); ++i) {
+      stc_lda* l = g->lda[(size_t)i];
+      g->ctx[(size_t)i]->use();
+      settle_side(*l);
+      wait_stream(*g->ctx[(size_t)i], g->ctx[(size_t)i]->stream);
+      forget_corpus(*l);
+    }
+    for (auto* d : g->shard) (void)stc_dcsr_free(d);
+    g->shard.clear();
+    g->rows = 0;
+  });
+}
+
+int stc_group_init_random(stc_group* g, uint64_t seed) {
+  return guard([&] {
+    STC_REQUIRE(g, "group");
+    for_members(*g, [&](int i) { member_ok(stc_lda_init_random(g->lda[(size_t)i], seed)); });
+  });
+}
+
+int stc_group_set_topics(stc_group* g, const double* topics, int layout) {
+  return guard([&] {
+    STC_REQUIRE(g && topics, "group/topics");
+    for_members(*g, [&](int i) { member_ok(stc_lda_set_topics(g->lda[(size_t)i], topics, layout)); });
+  });
+}
+
+int stc_group_get_topics(stc_group* g, double* topics_out, int layout) {
+  return guard([&] {
+    STC_REQUIRE(g && topics_out, "group/topics_out");
+    // gathering the sharded λ is collective: member 0 copies it out, the others only take part
+    for_members(*g, [&](int i) {
+      if (i == 0) member_ok(stc_lda_get_topics(g->lda[0], topics_out, layout));
+      else gather_lambda(*g->lda[(size_t)i]);
+    });
+  });
+}
+
+int stc_group_get_alpha(stc_group* g, double* alpha_out) {
+  return guard([&] {
+    STC_REQUIRE(g && alpha_out, "group/alpha_out");
+    require_usable(*g);
+    g->ctx[0]->use();
+    member_ok(stc_lda_get_alpha(g->lda[0], alpha_out));  // α is replicated on every member
+  });
+}
+
+int stc_group_get_iteration(stc_group* g, int64_t* iteration_out) {
+  return guard([&] {
+    STC_REQUIRE(g && iteration_out, "group/iteration_out");
+    member_ok(stc_lda_get_iteration(g->lda[0], iteration_out));
+  });
+}
+
+int stc_group_synchronize(stc_group* g) {
+  return guard([&] {
+    STC_REQUIRE(g, "group");
+    require_usable(*g);
+    for (int i = 0; i < g->n(); ++i) {
+      g->ctx[(size_t)i]->use();
+      wait_stream(*g->ctx[(size_t)i], g->ctx[(size_t)i]->stream);
+      if (hipStream_t side = side_stream(*g->lda[(size_t)i])) wait_stream(*g->ctx[(size_t)i], side);  // the next draw
+    }
+  });
+}
+
+static void merge_stats(stc_step_stats* out, const std::vector<stc_step_stats>& st) {
+  if (!out) return;
+  *out = stc_step_stats{};
+  for (const auto& s : st) {
+    out->batch_docs += s.batch_docs;
+    out->batch_entries += s.batch_entries;
+    out->inner_iters += s.inner_iters;
+    out->inner_iters_max = std::max(out->inner_iters_max, s.inner_iters_max);
+    out->cap_hits += s.cap_hits;
+  }
+  out->nonempty_docs = st[0].nonempty_docs;  // already summed over the members
+  out->rho = st[0].rho;
+}
+
+int stc_group_next(stc_group* g, stc_step_stats* stats) {
+  return guard([&] {
+    STC_REQUIRE(g, "group");
+    std::vector<stc_step_stats> st((size_t)g->n());
+    for_members(*g, [&](int i) { member_ok(stc_lda_next(g->lda[(size_t)i], stats ? &st[(size_t)i] : nullptr)); });
+    merge_stats(stats, st);
+  });
+}
+
+int stc_group_step(stc_group* g, const int64_t* batch_doc_ids, int64_t n, const double* gamma0, stc_step_stats* stats) {
+  return guard([&] {
+    STC_REQUIRE(g && (batch_doc_ids || n == 0) && n >= 0, "group/batch_doc_ids");
+    const int m = g->n();
+    const int64_t k = g->k;
+    std::vector<std::vector<int64_t>> ids((size_t)m);
+    std::vector<std::vector<double>> g0((size_t)m);
+    for (int64_t j = 0; j < n; ++j) {
+      const int64_t d = batch_doc_ids[j];
+      STC_REQUIRE(d >= 0 && d < g->rows, "batch doc id out of range");
+      const int q = (int)(std::upper_bound(g->row0.begin(), g->row0.end(), d) - g->row0.begin()) - 1;
+      ids[(size_t)q].push_back(d - g->row0[(size_t)q]);
+      if (gamma0) g0[(size_t)q].insert(g0[(size_t)q].end(), gamma0 + j * k, gamma0 + (j + 1) * k);
+    }
+    std::vector<stc_step_stats> st((size_t)m);
+    for_members(*g, [&](int i) {
+      const auto& v = ids[(size_t)i];
+      member_ok(stc_lda_step(g->lda[(size_t)i], v.data(), (int64_t)v.size(), gamma0 ? g0[(size_t)i].data() : nullptr,
+                             stats ? &st[(size_t)i] : nullptr));
+    });
+    merge_stats(stats, st);
+  });
+}
+
+int stc_group_describe(stc_group* g, int32_t max_terms, int32_t* idx_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(g && idx_out && weight_out, "group/idx_out/weight_out");
+    for_members(*g, [&](int i) {
+      if (i == 0) member_ok(stc_lda_describe(g->lda[0], max_terms, idx_out, weight_out));
+      else gather_lambda(*g->lda[(size_t)i]);
+    });
+  });
+}
+
+int stc_group_bound(stc_group* g, int64_t n_rows, int64_t n_cols, const int64_t* indptr, const int32_t* indices,
+                    const double* values, uint64_t gamma_seed, int64_t doc_id_base, const double* gamma0,
+                    double* bound_out, double* corpus_part_out, double* topics_part_out, double* token_count_out) {
+  return guard([&] {
+    STC_REQUIRE(g && bound_out, "group/bound_out");
+    check_host_csr(n_rows, n_cols, indptr, indices, values);
+    const std::vector<int64_t> r0 = shard_rows(indptr, n_rows, g->n());
+    const int64_t k = g->k;
+    double res[4] = {0, 0, 0, 0};
+    for_members(*g, [&](int i) {
+      const int64_t lo = r0[(size_t)i], hi = r0[(size_t)i + 1];
+      stc_dcsr* d = upload_rows(g->ctx[(size_t)i], lo, hi, n_cols, indptr, indices, values, g->dtype);
+      double r[4] = {0, 0, 0, 0};
+      // every member's γ₀ keys continue the global row numbering (doc_id_base + row), so the bound is
+      // the one a single handle computes over all rows
+      const int rc = stc_lda_bound(g->lda[(size_t)i], d, gamma_seed, doc_id_base + lo, gamma0 ? gamma0 + lo * k : nullptr,
+                                   &r[0], &r[1], &r[2], &r[3]);
+      (void)stc_dcsr_free(d);
+      member_ok(rc);
+      if (i == 0) std::copy(r, r + 4, res);  // the bound is all-reduced: every member holds the total
+    });
+    *bound_out = res[0];
+    if (corpus_part_out) *corpus_part_out = res[1];
+    if (topics_part_out) *topics_part_out = res[2];
+    if (token_count_out) *token_count_out = res[3];
+  });
+}
+
+int stc_group_topic_distribution(stc_group* g, int64_t n_rows, int64_t n_cols, const int64_t* indptr,
+                                 const int32_t* indices, const double* values, uint64_t gamma_seed,
+                                 int64_t doc_id_base, const double* gamma0, double* out) {
+  return guard([&] {
+    STC_REQUIRE(g && out, "group/out");
+    check_host_csr(n_rows, n_cols, indptr, indices, values);
+    const std::vector<int64_t> r0 = shard_rows(indptr, n_rows, g->n());
+    const int64_t k = g->k;
+    for_members(*g, [&](int i) {
+      const int64_t lo = r0[(size_t)i], hi = r0[(size_t)i + 1];
+      stc_dcsr* d = upload_rows(g->ctx[(size_t)i], lo, hi, n_cols, indptr, indices, values, g->dtype);
+      const int rc = stc_lda_topic_distribution(g->lda[(size_t)i], d, gamma_seed, doc_id_base + lo,
+                                                gamma0 ? gamma0 + lo * k : nullptr, out + lo * k);
+      (void)stc_dcsr_free(d);
+      member_ok(rc);
+    });
+  });
+}
+
+}  // extern "C"

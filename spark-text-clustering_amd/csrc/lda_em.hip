@@ -18,9 +18,8 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <memory>
 
-#include "lda_em.h"
+#include "stc_handles.h"
 
 namespace stc {
 namespace em {
@@ -344,10 +343,7 @@ inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)std::max
 inline unsigned strided_blocks(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>(1, ceil_div(n, 256)), 1 << 20); }
 
 void excl_scan(hipStream_t s, DevBuf& tmp, const int64_t* in, int64_t* out, int64_t n) {
-  size_t tb = 0;
-  HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, s));
-  tmp.reserve(tb);
-  HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, in, out, (int)n, s));
+  with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, in, out, (int)n, s); });
 }
 
 int pow2_at_least(int k) {
@@ -491,8 +487,6 @@ void require_idle_single(const Ctx& c) {
   if (c.coll()) throw Error(STC_ERR_STATE, "em: the context is connected to other ranks (EM is single-device)");
 }
 
-}  // namespace
-
 stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, double topic_concentration) {
   require_idle_single(c);
   STC_REQUIRE(in.dtype == STC_F64, "em: the corpus values must be STC_F64");
@@ -506,9 +500,7 @@ stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, doub
   STC_REQUIRE(eta > 1.0, "em: topicConcentration must be > 1.0 (or -1 for auto) for EM");
   c.use();
   hipStream_t s = c.stream;
-  auto m = std::make_unique<stc_em>();
-  m->ctx = &c;
-  m->device = c.device;
+  auto m = new_handle<stc_em>(c);
   m->k = k;
   m->D = in.rows;
   m->V = in.cols;
@@ -562,12 +554,10 @@ stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, doub
   if (E > 0) {
     int bits = 1;
     while ((int64_t(1) << bits) < m->V) ++bits;
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, m->rows.idx.as<int32_t>(), sorted_term.as<int32_t>(),
-                                                 iota.as<int64_t>(), m->cols.pos.as<int64_t>(), (int)E, 0, bits, s));
-    sort_tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(sort_tmp.p, tb, m->rows.idx.as<int32_t>(), sorted_term.as<int32_t>(),
-                                                 iota.as<int64_t>(), m->cols.pos.as<int64_t>(), (int)E, 0, bits, s));
+    with_temp(sort_tmp, [&](void* t, size_t& tb) {
+      return hipcub::DeviceRadixSort::SortPairs(t, tb, m->rows.idx.as<int32_t>(), sorted_term.as<int32_t>(),
+                                                iota.as<int64_t>(), m->cols.pos.as<int64_t>(), (int)E, 0, bits, s);
+    });
     k_em_transpose<<<blocks_for(E), 256, 0, s>>>(m->cols.pos.as<int64_t>(), erow.as<int32_t>(), m->rows.cnt.as<double>(),
                                                  E, m->cols.idx.as<int32_t>(), m->cols.cnt.as<double>());
     KERNEL_CHECK();
@@ -702,5 +692,67 @@ void shape(const stc_em& m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t
   if (n_edges) *n_edges = m.E;
 }
 
+}  // namespace
 }  // namespace em
 }  // namespace stc
+
+extern "C" {
+
+// ---- C ABI ---------------------------------------------------------------------------------
+int stc_em_create(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
+                  double topic_concentration, stc_em** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && corpus && out, "ctx/corpus/out");
+    STC_REQUIRE(corpus->ctx == ctx, "the corpus belongs to another stc_ctx");
+    *out = em::create(*ctx, *corpus, k, doc_concentration, topic_concentration);
+  });
+}
+
+int stc_em_destroy(stc_em* m) {
+  return guard([&] { em::destroy(m); });
+}
+
+int stc_em_shape(const stc_em* m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::shape(*m, k, n_docs, vocab, n_edges);
+  });
+}
+
+int stc_em_init_random(stc_em* m, uint64_t seed) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::init_random(*m, seed);
+  });
+}
+
+int stc_em_set_state(stc_em* m, const double* doc_topics, const double* term_topics) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::set_state(*m, doc_topics, term_topics);
+  });
+}
+
+int stc_em_get_state(stc_em* m, double* doc_topics, double* term_topics, double* totals, double* alpha_out,
+                     double* eta_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::get_state(*m, doc_topics, term_topics, totals, alpha_out, eta_out);
+  });
+}
+
+int stc_em_next(stc_em* m, int32_t n_iterations) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::next(*m, n_iterations);
+  });
+}
+
+int stc_em_log_likelihood(stc_em* m, double* log_likelihood_out, double* log_prior_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::log_likelihood(*m, log_likelihood_out, log_prior_out);
+  });
+}
+
+}  // extern "C"

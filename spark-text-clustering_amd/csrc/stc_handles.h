@@ -1,9 +1,15 @@
-// stc_handles.h — the ABI's opaque handles that more than one translation unit fills in (api.hip, text_prep.hip)
+// stc_handles.h — what the translation units behind the C ABI share beyond stc_internal.h: the opaque handles
+// that more than one of them fills in, and the host-side helpers of their entry points
 #pragma once
+
+#include <initializer_list>
+#include <memory>
+#include <utility>
 
 #include "stc_internal.h"
 
 struct stc_ctx : stc::Ctx {};
+struct stc_dcsr : stc::DCsr {};
 struct stc_dtok {
   stc::Ctx* ctx = nullptr;  // the context it was uploaded on / made by; only it may read the buffers
   int device = -1;          // for stc_tokens_free, which may run after that context is gone
@@ -12,3 +18,44 @@ struct stc_dtok {
   int64_t max_doc = -1;  // the longest document's token count (from the upload's offsets)
   bool off32 = false;    // tok_off holds u32 offsets (blob + padding < 4 GiB), else int64
 };
+
+namespace stc {
+
+template <typename H>
+std::unique_ptr<H> new_handle(Ctx& c) {  // an ABI handle made by, and readable only on, context c
+  auto h = std::make_unique<H>();
+  h->ctx = &c;
+  h->device = c.device;
+  return h;
+}
+
+struct TokenUpload {  // host tokens copied to the device for one call (features_api.hip)
+  DevBuf utf8, tok_off, doc_off;
+  int64_t max_doc = -1;  // the longest document's token count (doc_off given), −1 unknown
+};
+void upload_tokens(Ctx& c, TokenUpload& u, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off,
+                   int64_t n_tok, const int64_t* doc_off, int64_t n_docs);
+inline void swap(DevBuf& a, DevBuf& b) {
+  std::swap(a.p, b.p);
+  std::swap(a.bytes, b.bytes);
+}
+
+// The hipcub / rocprim two-call idiom: f(nullptr, bytes) asks for the temporary storage's size, tmp grows
+// to it, f(tmp.p, bytes) runs (unless run is false).  f: (void*, size_t&) -> hipError_t.
+template <typename F>
+void with_temp(DevBuf& tmp, F&& f, bool run = true) {
+  size_t bytes = 0;
+  HIP_CHECK(f(nullptr, bytes));
+  tmp.reserve(bytes);
+  if (run) HIP_CHECK(f(tmp.p, bytes));
+}
+
+// api.hip: off[0 .. n] of the host array `name` starts at 0, is non-decreasing and ends at `total` (spans) or
+// at most there; a host CSR's arrays (both return the largest gap: the longest document or row); and bufs'
+// allocations back to the recycler of the context that made them, if that context still exists on `device`
+int64_t check_offsets(const char* name, const int64_t* off, int64_t n, int64_t total, const char* total_name,
+                      bool spans);
+int64_t check_host_csr(int64_t rows, int64_t cols, const int64_t* indptr, const int32_t* indices, const double* values);
+void recycle_to(Ctx* ctx, int device, std::initializer_list<DevBuf*> bufs);
+
+}  // namespace stc

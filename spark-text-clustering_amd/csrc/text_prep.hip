@@ -29,7 +29,6 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <memory>
 
 #include "class_table.h"
 #include "stc_handles.h"
@@ -540,11 +539,8 @@ template <typename T>
 static void exclusive_sums(hipStream_t s, const T* in, T* out, int64_t n) {
   HIP_CHECK(hipMemsetAsync(out, 0, sizeof(T), s));
   if (n == 0) return;
-  size_t tb = 0;
-  HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, tb, in, out + 1, n, s));
   DevBuf tmp;
-  tmp.reserve(tb);
-  HIP_CHECK(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, in, out + 1, n, s));
+  with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::InclusiveSum(t, tb, in, out + 1, n, s); });
   HIP_CHECK(hipStreamSynchronize(s));  // tmp dies at scope exit
 }
 
@@ -581,10 +577,9 @@ static stc_prep* create(Ctx& c, const uint32_t* strip_cp, int64_t n_strip, const
   uint64_t slots = 2;
   std::vector<StopSlot> tab;
   if (n_stop > 0) {
-    STC_REQUIRE(stop_off[0] == 0 && stop_off[n_stop] == n_bytes, "stop_off must span [0, n_bytes]");
+    check_offsets("stop_off", stop_off, n_stop, n_bytes, "n_bytes", true);
     STC_REQUIRE(n_bytes == 0 || stop_utf8, "stop_utf8");
     for (int64_t w = 0; w < n_stop; ++w) {
-      STC_REQUIRE(stop_off[w + 1] >= stop_off[w], "stop_off must be non-decreasing");
       const int64_t r = first_bad_utf8(stop_utf8 + stop_off[w], stop_off[w + 1] - stop_off[w]);
       if (r >= 0) throw_bad_utf8("the stop words", stop_off[w] + r);
     }
@@ -606,9 +601,7 @@ static stc_prep* create(Ctx& c, const uint32_t* strip_cp, int64_t n_strip, const
     max_len = std::max(max_len, len);
   }
   c.use();
-  auto p = std::make_unique<stc_prep>();
-  p->ctx = &c;
-  p->device = c.device;
+  auto p = new_handle<stc_prep>(c);
   p->stem = stem;
   p->n_stop = n_stop;
   p->max_stop_len = max_len;
@@ -630,13 +623,10 @@ static stc_dtok* tokens(Ctx& c, const stc_prep& p, const uint8_t* text, int64_t 
   STC_REQUIRE(n >= 0 && n_docs >= 0, "sizes must be >= 0");
   STC_REQUIRE(n_docs < (int64_t(1) << 31) - 1, "at most 2^31-2 documents per call");
   STC_REQUIRE(text_off && (n == 0 || text), "text/text_off");
-  STC_REQUIRE(text_off[0] == 0 && text_off[n_docs] == n, "text_off must span [0, n_bytes]");
-  for (int64_t d = 0; d < n_docs; ++d) STC_REQUIRE(text_off[d + 1] >= text_off[d], "text_off must be non-decreasing");
+  check_offsets("text_off", text_off, n_docs, n, "n_bytes", true);
   c.use();
   hipStream_t s = c.stream;
-  auto t = std::make_unique<stc_dtok>();
-  t->ctx = &c;
-  t->device = c.device;
+  auto t = new_handle<stc_dtok>(c);
   t->n_docs = n_docs;
   t->doc_off.reserve(8 * (n_docs + 1));
   int64_t n_raw = 0, n_keep = 0, n_out = 0;
@@ -738,8 +728,7 @@ static void stem_tokens(Ctx& c, const uint8_t* utf8, int64_t n_bytes, const int6
   STC_REQUIRE(n_bytes >= 0 && n_tok >= 0, "sizes must be >= 0");
   STC_REQUIRE(n_tok <= (int64_t(1) << 31) - 1, "at most 2^31-1 tokens per call");
   STC_REQUIRE(tok_off && tok_off_out && (n_bytes == 0 || (utf8 && utf8_out)), "utf8/tok_off/outputs");
-  STC_REQUIRE(tok_off[0] == 0 && tok_off[n_tok] <= n_bytes, "tok_off must start at 0 and stay within n_bytes");
-  for (int64_t t = 0; t < n_tok; ++t) STC_REQUIRE(tok_off[t + 1] >= tok_off[t], "tok_off must be non-decreasing");
+  check_offsets("tok_off", tok_off, n_tok, n_bytes, "n_bytes", false);
   c.use();
   hipStream_t s = c.stream;
   DevBuf blob, off, bad, out_len, out_off, out, new_off;

@@ -20,7 +20,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "case_table.h"
-#include "stc_internal.h"
+#include "stc_handles.h"
 
 namespace stc {
 namespace tokenizer {
@@ -302,14 +302,11 @@ void tokenize(Ctx& c, const uint8_t* d_text, const int64_t* d_text_off, int64_t 
                                                       keep.as<int64_t>());
     KERNEL_CHECK();
   }
-  size_t tb = 0;
-  HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt.as<int64_t>(), out_doc_off.as<int64_t>(),
-                                             (int)(n_docs + 1), s));
-  tmp.reserve(tb);
-  HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, cnt.as<int64_t>(), out_doc_off.as<int64_t>(),
-                                             (int)(n_docs + 1), s));
-  HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, keep.as<int64_t>(), byte_off.as<int64_t>(),
-                                             (int)(n_docs + 1), s));
+  auto scan = [&](const int64_t* in, int64_t* out) {
+    with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, in, out, (int)(n_docs + 1), s); });
+  };
+  scan(cnt.as<int64_t>(), out_doc_off.as<int64_t>());
+  scan(keep.as<int64_t>(), byte_off.as<int64_t>());
   int64_t h[2];
   HIP_CHECK(hipMemcpyAsync(&h[0], out_doc_off.as<int64_t>() + n_docs, 8, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(&h[1], byte_off.as<int64_t>() + n_docs, 8, hipMemcpyDeviceToHost, s));

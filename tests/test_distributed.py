@@ -4,7 +4,7 @@ The product shards a minibatch by document.  E
 * runs the E-step on its members;
 * accumulates its partial `stat` (V×k), logphat and non-empty count;
 * joins a reduce-scatter of `stat` over vocabulary slices of Vs rows (Vs a multiple of the 64-row
-  λ-update block) grouped with the all-reduce of logphat / count (api.hip train_tail);
+  λ-update block) grouped with the all-reduce of logphat / count (lda_online.hip train_tail);
 * updates λ on its slice, all-gathers the per-block colsum partials (reduced in block order, so every
   rank holds the same colsum), computes its slice of expElogβ and all-gathers it for the next E-step;
 * gathers λ only when a reader asks (gather_lambda); the bound sums each slice's topics part.
@@ -128,7 +128,7 @@ def _worker(rank, world, port, out_dir):
     idf = np.where(df.numpy() >= mdf, np.log((int(m) + 1.0) / (df.numpy() + 1.0)), 0.0)
 
     # --- bound: corpus part over the rank's documents; topics part: the element sum over the rank's
-    # vocabulary slice (λ sharded), both all-reduced, plus the per-topic normaliser once (api.hip
+    # vocabulary slice (λ sharded), both all-reduced, plus the per-topic normaliser once (lda_online.hip
     # topics_part / stc_lda_bound)
     bdocs = [corpus.row(int(r)) for r in rows]
     bg0 = np.stack([O.gamma_init(11, int(r), k) for r in rows])

@@ -283,7 +283,7 @@ def test_hashing_tf_single_pass_orders_and_fallback(ctx, monkeypatch):
 
 
 def test_recycled_output_buffers_carry_no_stale_data(ctx, oracle):
-    """A freed stc_dcsr / stc_didf hands its allocations back to the context (api.hip Recycler); the next
+    """A freed stc_dcsr / stc_didf hands its allocations back to the context (api.hip recycle_to); the next
     HashingTF / IDF outputs of similar size reuse them: results of a large corpus, then a smaller one,
     then the large one again, each equal to the oracle (no entry of an earlier output survives)."""
     import stc
