@@ -26,6 +26,17 @@
 // reload the old loop carried; the cost is LDS traffic (13 8-byte stores per lane and iteration),
 // which the LDS array absorbs beside the VALU (MI355X_MICROARCH.md §LDS).
 // Numerics as lda.hip: Bp row-scaled by e^{-m_v}, Spark's 1e-100 carried as ε'_n = 1e-100·e^{-m_v}.
+//
+// LDS of the fixed point (RLds::u.l; the load phase's staging rows lie over all of it):
+//   wv[w]  wave w's own rows, touched by no other wave: pa[wave row][topic lane] (pitch 10 doubles), the φ
+//          partials of Phase A; with R64_SB_LDS the same bytes are sx[topic][row lane] (pitch 10) in Phase B,
+//          when pa is dead (the worker lanes have read it, the wave's next Phase A lies behind both block
+//          barriers).  wv[w] is sized for the larger of the two.
+//   sb     [topic][wave] (pitch 4): each wave's sum of its eight row lanes' s partials, written before block
+//          barrier 1 and read by the ψ / mirror lanes after it.  Never aliased by a wave's own rows.
+// R64_SB_LDS chooses how a wave forms those sums: 0 (shipped) the in-register reduce-scatter rs_rows8,
+// 1 through sx; both add a topic's eight partials as ((x0 + x4) + (x2 + x6)) + ((x1 + x5) + (x3 + x7)), so
+// every output is bitwise the same (DESIGN.md §3 "r07": fewer VALU instructions, not faster).
 #include "estep_common.h"
 #include "psi64.h"
 
@@ -43,6 +54,16 @@
                       // r04 measured it +1.3 % (31.96 vs 31.54 ms, off then); after the in-wave s
                       // reduce-scatter and the resident grid it is −4 %: headline E-step 27.05 → 25.97 ms
 #endif
+#ifndef R64_SB_LDS
+#define R64_SB_LDS 0  // 1: the eight row lanes' s partials are summed through the wave's own LDS rows (sx) in
+                      // rs_rows8's order (bitwise the same); 0: by the in-register reduce-scatter (estep_common.h
+                      // rs_rows8).  r07: 1 executes 18 % fewer VALU instructions and is not faster (headline
+                      // 28.00 vs 27.90 ms; [row lane][topic] rows 29.17 ms): DESIGN.md §3 "r07"
+#endif
+#ifndef R64_PSI_TPL
+#define R64_PSI_TPL 1  // 1: the number of ψ waves is a template parameter (the ψ / mirror role tests are scalar
+                       // code or constants); 0: read from kp at run time.  r07: headline 27.35 vs 27.90 ms
+#endif
 #ifndef R64_LONG_OCC
 #define R64_LONG_OCC 1  // long-document kernel workgroups per CU the register budget is cut for
 #endif
@@ -57,6 +78,13 @@ constexpr int kSbPitch = 4;   // s-partial row pitch (doubles): one sum per wave
 constexpr int kPaPitch = 10;   // φ-partial row pitch (doubles): conflict-free 16-B worker reads
 constexpr int kOnChipSets = 6; // row sets the common kernel holds (5 in VGPRs + 1 in LDS)
 constexpr int kMaxSets = 8;    // one worker lane per wave row: 8 row lanes × 8 sets = 64 lanes
+
+// R64_SB_LDS: a wave's s partials sx[topic][row lane] at kSxPitch doubles per topic.  The 16 lanes of a
+// ds_write_b64 group (eight topic lanes × two row lanes) store at double slots 10·KL·tl + rl ≡ 2·(KL·tl mod 8) + rl
+// (mod 16): all distinct for odd KL, two lanes per slot for KL = 4; the reducer's ds_read_b128 (16 lanes per
+// group, one of each residue mod 16, lane pitch 80 B = 5 16-byte slots) is conflict-free.  Measured: no
+// SQ_LDS_BANK_CONFLICT cycle more than with the switch off (profiles/r07_counters.json).
+constexpr int kSxPitch = 10;
 
 template <int KL_, int RREG_, int RMAX_>
 struct RShape {
@@ -87,10 +115,14 @@ struct RLds {
   PsiK psik;                       // the exp() constants of the ψ chain (psi_expk_load)
   union {
     struct {
-      double pa[kW][8 * S::RMAX][kPaPitch];  // φ partials (wave, wave row, topic lane)
-      double sb[S::KT][kSbPitch];            // s partials (topic, row lane 8·w + rl)
+      union {                                // one wave's own rows: no other wave reads or writes them
+        double pa[8 * S::RMAX][kPaPitch];    // Phase A: φ partials (wave row, topic lane)
+        // Phase B (R64_SB_LDS): s partials (topic, row lane); pa is dead by then
+        double sx[R64_SB_LDS ? S::KT * kSxPitch : 1] __attribute__((aligned(16)));
+      } wv[kW];
+      double sb[S::KT][kSbPitch];            // s partials (topic, wave): what the ψ lanes read
     } l;
-    double stage[kW][8][S::KT + 2];          // load phase: eight B rows per wave at a time
+    double stage[kW][8][S::KT + 2];          // load phase: eight B rows per wave at a time (over all of l)
   } u __attribute__((aligned(16)));
   double ovf[S::NOVF > 0 ? S::NOVF * kW * S::KL * 64 : 1];  // row sets past RREG ([set][w][p][lane])
 };
@@ -123,7 +155,8 @@ __device__ __forceinline__ int rows64_tid(const RDoc& d) { return RES ? d.tid : 
 
 // worker lanes, γ₀, α / ψc, Σγ₀ / Σα / Σcts, the first eθ; false (outputs written) for a document
 // without a nonzero count
-template <class S, bool STATS, bool BOUND, bool RES>
+// NPSI (here and below): the number of ψ waves, 2 for kp > 64, else 1; 0 reads it from kp at run time
+template <class S, bool STATS, bool BOUND, bool RES, int NPSI>
 __device__ __forceinline__ bool rows64_open(const EStepArgs<double>& a, RLds<S>& sm, RDoc& d) {
   const int tid = rows64_tid<RES>(d);
   constexpr int KL = S::KL, KLP = S::KLP;
@@ -136,7 +169,7 @@ __device__ __forceinline__ bool rows64_open(const EStepArgs<double>& a, RLds<S>&
   d.tl = lane & 7;
   d.rl = lane >> 3;
   // ψ-lane topic map: k > 64 two ψ waves of `half` topics (t = (w & 1)·half + lane), else one
-  d.npsi = kp > 64 ? 2 : 1;
+  d.npsi = NPSI ? NPSI : (kp > 64 ? 2 : 1);
   d.half = d.npsi == 2 ? (kp + 1) / 2 : kp;
   d.pw = d.npsi == 2 ? (w & 1) : 0;
   d.tt = d.pw * d.half + lane;
@@ -226,9 +259,10 @@ __device__ __forceinline__ bool rows64_open(const EStepArgs<double>& a, RLds<S>&
 
 // the document block (R row sets) and the fixed point; returns the iteration count, the worker's φ
 // (without ε') in qdt; the final r sits in sm.rrow
-template <class S, int R>
+template <class S, int R, int NPSI>
 __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S>& sm, RDoc& d, double& qdt) {
   constexpr int KL = S::KL, KLP = S::KLP;
+  static_assert(NPSI < 2 || S::KT > 64, "two ψ waves: kp > 64");
   constexpr int RG = R < S::RREG ? R : S::RREG;  // row sets in VGPRs; [RG, R) in sm.ovf
   static_assert(R >= 1 && R <= S::RMAX && R - RG <= S::NOVF, "row sets");
   STAMP_DECL
@@ -236,7 +270,9 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
   st_acc[10] += st_last - d.st0;
 #endif
   const int lane = d.lane, w = d.w, tl = d.tl, rl = d.rl;
-  const int k = a.k, kp = a.kp, nnz = d.nnz, npsi = d.npsi, pw = d.pw, tt = d.tt, ttl = d.ttl, ttp = d.ttp;
+  const int k = a.k, kp = a.kp, nnz = d.nnz, tt = d.tt, ttl = d.ttl, ttp = d.ttp;
+  // the ψ / mirror / dsum role tests below are on w, it and npsi only: with npsi a constant they are scalar
+  const int npsi = NPSI ? NPSI : d.npsi, pw = NPSI ? (NPSI == 2 ? (w & 1) : 0) : d.pw;
   const bool town = d.town;
   const int qid = d.qid;
   const double qc = d.qc;
@@ -312,7 +348,8 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
     em = sm.eth[ttl][ttp];
   }
 
-  double* const pa = &sm.u.l.pa[w][0][0];
+  double* const pa = &sm.u.l.wv[w].pa[0][0];
+  double* const paw = pa + rl * kPaPitch + tl;  // the lane's φ-partial slot of row set 0 (set j: 8 rows on)
   double* const sb = &sm.u.l.sb[0][0];
   const PsiExpK expk = psi_expk_load(sm.psik);
   double rr[R];
@@ -328,31 +365,66 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
       double acc[R];
 #pragma unroll
       for (int j = 0; j < R; ++j) acc[j] = 0.0;
+      // With a row set in LDS the step's eθ pair and B values are read one step ahead and the steps are
+      // fenced: left to itself the scheduler reads all KL of both up front, 54 VGPRs beside the block's
+      // 26·RG, and the document context held across the loop spills.
+      constexpr bool OVP = R64_SB_LDS != 0 && R > RG;
+      constexpr int NO = OVP ? 2 * (R - RG) : 1;
+      double2 en = make_double2(0.0, 0.0);
+      double on[NO] = {};
+      if constexpr (OVP) {
+        en = *reinterpret_cast<const double2*>(&sm.eth[tl][0]);
 #pragma unroll
-      for (int c = 0; c < KLP / 2; ++c) {
-        const double2 e = *reinterpret_cast<const double2*>(&sm.eth[tl][2 * c]);
-#pragma unroll
-        for (int j = 0; j < R; ++j) {
-          acc[j] = fma(BV(j, 2 * c), e.x, acc[j]);
-          if (2 * c + 1 < KL) acc[j] = fma(BV(j, 2 * c + 1), e.y, acc[j]);
+        for (int j = RG; j < R; ++j) {
+          on[2 * (j - RG)] = BV(j, 0);
+          if (1 < KL) on[2 * (j - RG) + 1] = BV(j, 1);
         }
       }
 #pragma unroll
-      for (int j = 0; j < R; ++j) pa[(8 * j + rl) * kPaPitch + tl] = acc[j];
+      for (int c = 0; c < KLP / 2; ++c) {
+        const double2 e = OVP ? en : *reinterpret_cast<const double2*>(&sm.eth[tl][2 * c]);
+        double oc[NO];
+#pragma unroll
+        for (int i = 0; i < NO; ++i) oc[i] = on[i];
+        if (OVP && c + 1 < KLP / 2) {
+          en = *reinterpret_cast<const double2*>(&sm.eth[tl][2 * c + 2]);
+#pragma unroll
+          for (int j = RG; j < R; ++j) {
+            on[2 * (j - RG)] = BV(j, 2 * c + 2 < KL ? 2 * c + 2 : 0);
+            if (2 * c + 3 < KL) on[2 * (j - RG) + 1] = BV(j, 2 * c + 3 < KL ? 2 * c + 3 : 0);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          const int jo = OVP && j >= RG ? 2 * (j - RG) : 0;
+          acc[j] = fma(OVP && j >= RG ? oc[jo] : BV(j, 2 * c), e.x, acc[j]);
+          if (2 * c + 1 < KL) acc[j] = fma(OVP && j >= RG ? oc[jo + 1] : BV(j, 2 * c + 1), e.y, acc[j]);
+        }
+        if (OVP) __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int j = 0; j < R; ++j) paw[8 * kPaPitch * j] = acc[j];
     }
     STAMP(1);  // eθ reads, φ FMAs, partial stores
     __builtin_amdgcn_wave_barrier();
     if (R64_PRIO >= 2) __builtin_amdgcn_s_setprio(3);
-    bool live = false;
     if (lane < 8 * R) {
       const double2* const pr = reinterpret_cast<const double2*>(pa + lane * kPaPitch);
       const double2 x0 = pr[0], x1 = pr[1], x2 = pr[2], x3 = pr[3];
       qdt = ((x0.x + x0.y) + (x1.x + x1.y)) + ((x2.x + x2.y) + (x3.x + x3.y));
       const double ph = fma(qe2, 0x1p-53, qdt);
       qr = qc * rcp_nr(ph);
-      live = qe2 >= ph;  // ε' visible at fp64 resolution
       sm.rrow[w][lane] = qr;
     }
+    // ε' visible at fp64 resolution: the worker's test 2^53·ε' ≥ φ, formed for every lane (the others hold
+    // 2^53·ε' = −2^53 and qdt = 0: never live) so the compare's lane mask is the ballot itself, not a
+    // per-lane flag carried out of the branch above and compared again
+#if R64_PSI_TPL
+    const bool live = qe2 >= fma(qe2, 0x1p-53, qdt);
+#else
+    bool live = false;
+    if (lane < 8 * R) live = qe2 >= fma(qe2, 0x1p-53, qdt);
+#endif
     if (__builtin_amdgcn_ballot_w64(live) != 0) {
       const double e = wave_sum_d(lane < 8 * R ? qr * (qe2 * 0x1p-53) : 0.0);
       if (lane == 0) sm.esum[w] = e;
@@ -369,6 +441,41 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
     if ((it > 0 && dsum <= a.stop_thr) || it >= a.max_iter) break;
 
     // Phase B: s partials over the lane's R rows, one row lane's slot per topic
+#if R64_SB_LDS
+    {  // the eight row lanes summed through the wave's own LDS rows (over its dead φ partials: the worker
+       // lanes read those before the wave barrier above, and its next Phase A lies behind both block
+       // barriers): every lane stores each of its KL sums as its R FMAs finish, then lane l adds the eight
+       // row lanes' partials of topics l and l + 64 in rs_rows8's order (row-lane bit 2, then 1, then 0:
+       // bitwise the same sums) and stores the wave's sum where the ψ lanes read it
+      double* const sx = &sm.u.l.wv[w].sx[0];
+      double* const sxw = sx + KL * tl * kSxPitch + rl;
+      // a row set in LDS is read before the first store (a read cannot move up past a store to the same
+      // array: one LDS round trip per topic otherwise)
+      double ov[R > RG ? R - RG : 1][KL];
+#pragma unroll
+      for (int j = RG; j < R; ++j) {
+#pragma unroll
+        for (int p = 0; p < KL; ++p) ov[j - RG][p] = BV(j, p);
+      }
+#pragma unroll
+      for (int p = 0; p < KL; ++p) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < R; ++j) acc = fma(j < RG ? BV(j, p) : ov[j < RG ? 0 : j - RG][p], rr[j], acc);
+        sxw[p * kSxPitch] = acc;
+      }
+      __builtin_amdgcn_wave_barrier();  // one wave writes and reads its rows; LDS is in order per wave
+#pragma unroll
+      for (int h = (S::KT - 1) / 64; h >= 0; --h) {
+        const int t = lane + 64 * h;
+        if (S::KT >= 64 * (h + 1) || t < S::KT) {
+          const double2* const xr = reinterpret_cast<const double2*>(sx + t * kSxPitch);
+          const double2 x01 = xr[0], x23 = xr[1], x45 = xr[2], x67 = xr[3];
+          sb[t * kSbPitch + w] = ((x01.x + x45.x) + (x23.x + x67.x)) + ((x01.y + x45.y) + (x23.y + x67.y));
+        }
+      }
+    }
+#else
     {  // the eight row lanes summed inside the wave (estep_common.h rs_rows8): lane (tl, rl) stores the wave
        // sums of its topic lane's topics 2·rl, 2·rl + 1, so a ψ lane reads 4 partials instead of 32
       double x[16];
@@ -386,6 +493,7 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
       if (2 * rl < KL) sb[(KL * tl + 2 * rl) * kSbPitch + w] = s0;
       if (2 * rl + 1 < KL) sb[(KL * tl + 2 * rl + 1) * kSbPitch + w] = s1;
     }
+#endif
     STAMP(3);  // s FMAs + partial stores
     __syncthreads();  // (1) s partials and esum published
     STAMP(4);  // barrier 1
@@ -532,29 +640,29 @@ __device__ __forceinline__ void rows64_close(const EStepArgs<double>& a, RLds<S>
 
 // one document (slot, row, member and extent set by the caller): open → iterate<R> → close
 // LONG: the 7–8-row-set documents; RES: a resident kernel (d.tid laundered per document)
-template <class S, bool STATS, bool BOUND, bool LONG, bool RES = LONG>
+template <class S, bool STATS, bool BOUND, int NPSI, bool LONG, bool RES = LONG>
 __device__ __forceinline__ void rows64_doc(const EStepArgs<double>& a, RLds<S>& sm, RDoc& d) {
   d.e0 = a.bptr ? a.bptr[d.slot] : d.s0;
-  if (!rows64_open<S, STATS, BOUND, RES>(a, sm, d)) return;
+  if (!rows64_open<S, STATS, BOUND, RES, NPSI>(a, sm, d)) return;
   double qdt = 0.0;
   int it;
   if constexpr (LONG) {
-    it = d.rsets == 7 ? rows64_iterate<S, 7>(a, sm, d, qdt) : rows64_iterate<S, 8>(a, sm, d, qdt);
+    it = d.rsets == 7 ? rows64_iterate<S, 7, NPSI>(a, sm, d, qdt) : rows64_iterate<S, 8, NPSI>(a, sm, d, qdt);
   } else {
     switch (d.rsets) {
-      case 1: it = rows64_iterate<S, 1>(a, sm, d, qdt); break;
-      case 2: it = rows64_iterate<S, 2>(a, sm, d, qdt); break;
-      case 3: it = rows64_iterate<S, 3>(a, sm, d, qdt); break;
-      case 4: it = rows64_iterate<S, 4>(a, sm, d, qdt); break;
-      case 5: it = rows64_iterate<S, 5>(a, sm, d, qdt); break;
-      default: it = rows64_iterate<S, 6>(a, sm, d, qdt); break;
+      case 1: it = rows64_iterate<S, 1, NPSI>(a, sm, d, qdt); break;
+      case 2: it = rows64_iterate<S, 2, NPSI>(a, sm, d, qdt); break;
+      case 3: it = rows64_iterate<S, 3, NPSI>(a, sm, d, qdt); break;
+      case 4: it = rows64_iterate<S, 4, NPSI>(a, sm, d, qdt); break;
+      case 5: it = rows64_iterate<S, 5, NPSI>(a, sm, d, qdt); break;
+      default: it = rows64_iterate<S, 6, NPSI>(a, sm, d, qdt); break;
     }
   }
   rows64_close<S, STATS, BOUND, RES>(a, sm, d, it, qdt);
 }
 
 // the documents with ≤ kOnChipSets row sets: one workgroup per slot (the long documents exit at once)
-template <class S, bool STATS, bool BOUND>
+template <class S, bool STATS, bool BOUND, int NPSI>
 __global__ __launch_bounds__(64 * kW, 2) void k_estep_rows64(EStepArgs<double> a) {
   __shared__ RLds<S> sm;
   if ((int64_t)blockIdx.x >= a.n) return;
@@ -569,7 +677,7 @@ __global__ __launch_bounds__(64 * kW, 2) void k_estep_rows64(EStepArgs<double> a
   d.nnz = (int)(a.indptr[d.row + 1] - d.s0);
   d.rsets = (d.nnz + 31) >> 5;
   if (d.rsets > kOnChipSets) return;  // the long-document kernel's
-  rows64_doc<S, STATS, BOUND, false>(a, sm, d);
+  rows64_doc<S, STATS, BOUND, NPSI, false>(a, sm, d);
 }
 
 // The same documents on a resident grid: every workgroup takes the next slot from a ticket counter and
@@ -577,7 +685,7 @@ __global__ __launch_bounds__(64 * kW, 2) void k_estep_rows64(EStepArgs<double> a
 // per slot paid a dispatch and its own prologue start per document; here the next ticket is requested at
 // the start of a document and read at its end, and the per-document lane maps are laundered (as in the
 // long-document kernel) so they are not hoisted and held across the fixed point.
-template <class S, bool STATS, bool BOUND>
+template <class S, bool STATS, bool BOUND, int NPSI>
 __global__ __launch_bounds__(64 * kW, 2) void k_estep_rows64_pers(EStepArgs<double> a, int32_t* ticket) {
   __shared__ RLds<S> sm;
   __shared__ int s_tk;
@@ -600,7 +708,7 @@ __global__ __launch_bounds__(64 * kW, 2) void k_estep_rows64_pers(EStepArgs<doub
     d.s0 = a.indptr[d.row];
     d.nnz = (int)(a.indptr[d.row + 1] - d.s0);
     d.rsets = (d.nnz + 31) >> 5;
-    if (d.rsets <= kOnChipSets) rows64_doc<S, STATS, BOUND, false, true>(a, sm, d);
+    if (d.rsets <= kOnChipSets) rows64_doc<S, STATS, BOUND, NPSI, false, true>(a, sm, d);
     if (threadIdx.x == 0) s_tk = nxt;
     __syncthreads();  // LDS is the next document's; s_tk published
     cur = s_tk;
@@ -620,7 +728,7 @@ __global__ void k_rows64_long_list(EStepArgs<double> a) {
 
 // the 7–8-set documents at one workgroup per CU, a resident grid walking the list (a grid over every
 // slot would dispatch ~n workgroups at that occupancy only to have most exit after two dependent loads)
-template <class S, bool STATS, bool BOUND>
+template <class S, bool STATS, bool BOUND, int NPSI>
 __global__ __launch_bounds__(64 * kW, R64_LONG_OCC) void k_estep_rows64_long(EStepArgs<double> a) {
   __shared__ RLds<S> sm;
   const int cnt = a.long_list[0];
@@ -639,12 +747,12 @@ __global__ __launch_bounds__(64 * kW, R64_LONG_OCC) void k_estep_rows64_long(ESt
     d.s0 = a.indptr[d.row];
     d.nnz = (int)(a.indptr[d.row + 1] - d.s0);
     d.rsets = (d.nnz + 31) >> 5;
-    rows64_doc<S, STATS, BOUND, true>(a, sm, d);
+    rows64_doc<S, STATS, BOUND, NPSI, true>(a, sm, d);
     __syncthreads();  // LDS is the next document's
   }
 }
 
-template <class S>
+template <class S, int NPSI>
 bool launch_persist(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bound) {
   if (!a.long_list || bound) return false;  // (the bound E-step keeps a workgroup per slot)
   int32_t* ticket = a.long_list + a.n + 1;  // the word past the long-document list (api.hip reserves it)
@@ -661,20 +769,20 @@ bool launch_persist(hipStream_t s, const EStepArgs<double>& a, bool stats, bool 
     HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(64 * kW), args, 0, s));
     return true;
   };
-  if (stats) return go((const void*)k_estep_rows64_pers<S, true, false>);
-  return go((const void*)k_estep_rows64_pers<S, false, false>);
+  if (stats) return go((const void*)k_estep_rows64_pers<S, true, false, NPSI>);
+  return go((const void*)k_estep_rows64_pers<S, false, false, NPSI>);
 }
-template <class S>
+template <class S, int NPSI>
 void launch_common(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bound) {
-  if (launch_persist<S>(s, a, stats, bound)) return;
+  if (launch_persist<S, NPSI>(s, a, stats, bound)) return;
   const dim3 grid((unsigned)a.n);
   const int threads = 64 * kW;
-  if (stats) k_estep_rows64<S, true, false><<<grid, threads, 0, s>>>(a);
-  else if (bound) k_estep_rows64<S, false, true><<<grid, threads, 0, s>>>(a);
-  else k_estep_rows64<S, false, false><<<grid, threads, 0, s>>>(a);
+  if (stats) k_estep_rows64<S, true, false, NPSI><<<grid, threads, 0, s>>>(a);
+  else if (bound) k_estep_rows64<S, false, true, NPSI><<<grid, threads, 0, s>>>(a);
+  else k_estep_rows64<S, false, false, NPSI><<<grid, threads, 0, s>>>(a);
   KERNEL_CHECK();
 }
-template <class S>
+template <class S, int NPSI>
 void launch_long(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bound) {
   if (!a.long_list) throw Error(STC_ERR_STATE, "fp64 rows E-step: no long-document list buffer");
   HIP_CHECK(hipMemsetAsync(a.long_list, 0, sizeof(int32_t), s));
@@ -685,16 +793,16 @@ void launch_long(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bou
   HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(a.n, (int64_t)cus * R64_LONG_OCC)));
   const int threads = 64 * kW;
-  if (stats) k_estep_rows64_long<S, true, false><<<grid, threads, 0, s>>>(a);
-  else if (bound) k_estep_rows64_long<S, false, true><<<grid, threads, 0, s>>>(a);
-  else k_estep_rows64_long<S, false, false><<<grid, threads, 0, s>>>(a);
+  if (stats) k_estep_rows64_long<S, true, false, NPSI><<<grid, threads, 0, s>>>(a);
+  else if (bound) k_estep_rows64_long<S, false, true, NPSI><<<grid, threads, 0, s>>>(a);
+  else k_estep_rows64_long<S, false, false, NPSI><<<grid, threads, 0, s>>>(a);
   KERNEL_CHECK();
 }
 // the 7–8-set documents first (`long_docs` = false when the caller knows there are none), then the rest
-template <int KL>
+template <int KL, int NPSI>
 void launch_r(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bound, bool long_docs) {
-  if (long_docs) launch_long<RLong<KL>>(s, a, stats, bound);
-  launch_common<RCommon<KL>>(s, a, stats, bound);
+  if (long_docs) launch_long<RLong<KL>, NPSI>(s, a, stats, bound);
+  launch_common<RCommon<KL>, NPSI>(s, a, stats, bound);
 }
 
 }  // namespace
@@ -705,9 +813,12 @@ int rows64_onchip_rows(int k) { return k <= 104 ? 32 * kOnChipSets : 0; }
 void launch_estep_rows64(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bound, bool long_docs) {
   if (a.n == 0) return;
   if (a.kp > 8 * 13 || a.kp < a.k || (a.kp & 1)) throw Error(STC_ERR_INVALID_ARG, "fp64 rows E-step: bad k / kp");
-  if (a.k <= 32) launch_r<4>(s, a, stats, bound, long_docs);
-  else if (a.k <= 56) launch_r<7>(s, a, stats, bound, long_docs);
-  else launch_r<13>(s, a, stats, bound, long_docs);
+  // only the (KL, ψ waves) pairs that occur: KL = 4 and 7 have kp ≤ 64 (one ψ wave), KL = 13 either
+  constexpr int kOne = R64_PSI_TPL ? 1 : 0, kTwo = R64_PSI_TPL ? 2 : 0;
+  if (a.k <= 32) launch_r<4, kOne>(s, a, stats, bound, long_docs);
+  else if (a.k <= 56) launch_r<7, kOne>(s, a, stats, bound, long_docs);
+  else if (kTwo == 0 || a.kp > 64) launch_r<13, kTwo>(s, a, stats, bound, long_docs);
+  else launch_r<13, kOne>(s, a, stats, bound, long_docs);
 }
 
 STC_STAMP_READER(stc_debug_stamps_rows64)
