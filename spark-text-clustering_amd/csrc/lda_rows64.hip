@@ -28,17 +28,19 @@
 // Numerics as lda.hip: Bp row-scaled by e^{-m_v}, Spark's 1e-100 carried as ε'_n = 1e-100·e^{-m_v}.
 //
 // LDS of the fixed point (RLds::u.l; the load phase's staging rows lie over all of it):
-//   wv[w]  wave w's own rows, touched by no other wave: pa[wave row][topic lane] (pitch 10 doubles), the φ
-//          partials of Phase A; with R64_SB_LDS the same bytes are sx[topic][row lane] (pitch 10) in Phase B,
+//   wv[w]  wave w's own rows, touched by no other wave: pa[wave row][topic lane] (80 doubles per row set, the
+//          rows inside it placed by rows64_layout.h pa_row), the φ partials of Phase A; with R64_SB_LDS the same bytes are sx[topic][row lane] (pitch 10) in Phase B,
 //          when pa is dead (the worker lanes have read it, the wave's next Phase A lies behind both block
 //          barriers).  wv[w] is sized for the larger of the two.
 //   sb     [topic][wave] (pitch 4): each wave's sum of its eight row lanes' s partials, written before block
-//          barrier 1 and read by the ψ / mirror lanes after it.  Never aliased by a wave's own rows.
+//          barrier 1 and read by the ψ / mirror lanes after it.  Never aliased by a wave's own rows.  The wave
+//          slot is swizzled per topic (rows64_layout.h sb_slot) so neither side has an LDS bank conflict.
 // R64_SB_LDS chooses how a wave forms those sums: 0 (shipped) the in-register reduce-scatter rs_rows8,
 // 1 through sx; both add a topic's eight partials as ((x0 + x4) + (x2 + x6)) + ((x1 + x5) + (x3 + x7)), so
 // every output is bitwise the same (DESIGN.md §3 "r07": fewer VALU instructions, not faster).
 #include "estep_common.h"
 #include "psi64.h"
+#include "rows64_layout.h"
 
 #ifndef R64_LOAD_BATCH
 #define R64_LOAD_BATCH 3  // row sets whose B loads are in flight together in the load phase (r03: 2 → 3, −2 %)
@@ -64,6 +66,16 @@
 #define R64_PSI_TPL 1  // 1: the number of ψ waves is a template parameter (the ψ / mirror role tests are scalar
                        // code or constants); 0: read from kp at run time.  r07: headline 27.35 vs 27.90 ms
 #endif
+#ifndef R64_SB_SWZ
+#define R64_SB_SWZ 1  // 1: a wave stores its sum of topic t at sb[t][w ^ f(t)] and a ψ / mirror lane reads its
+                      // record's two 16-byte halves in a per-lane order (rows64_layout.h: no bank conflict in the
+                      // stores or the reads, per-lane address constants only, bitwise the same sums); 0: sb[t][w]
+                      // (4-way stores, 2-way reads).  DESIGN.md §3 "r08"
+#endif
+#ifndef R64_PA_LAYOUT
+#define R64_PA_LAYOUT 1  // 1: the φ-partial rows of a set start at 18·(rl >> 1) + 8·(rl & 1) doubles (stores and
+                         // worker reads conflict-free, same footprint); 0: at 10·rl (2-way stores)
+#endif
 #ifndef R64_LONG_OCC
 #define R64_LONG_OCC 1  // long-document kernel workgroups per CU the register budget is cut for
 #endif
@@ -74,8 +86,8 @@ namespace lda {
 namespace {
 
 constexpr int kW = 4;          // waves per document
-constexpr int kSbPitch = 4;   // s-partial row pitch (doubles): one sum per wave (rs_rows8), 16-B reads
-constexpr int kPaPitch = 10;   // φ-partial row pitch (doubles): conflict-free 16-B worker reads
+using r64::kPaPitch;  // φ-partial rows and the s partials sb[topic][wave]: rows64_layout.h, with their bank model
+using r64::kSbPitch;
 constexpr int kOnChipSets = 6; // row sets the common kernel holds (5 in VGPRs + 1 in LDS)
 constexpr int kMaxSets = 8;    // one worker lane per wave row: 8 row lanes × 8 sets = 64 lanes
 
@@ -349,8 +361,28 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
   }
 
   double* const pa = &sm.u.l.wv[w].pa[0][0];
-  double* const paw = pa + rl * kPaPitch + tl;  // the lane's φ-partial slot of row set 0 (set j: 8 rows on)
+  // the lane's φ-partial slot of row set 0 (set j: 8 rows on) and, a worker lane's, its row: byte offsets
+  int paw_o = 8 * (r64::pa_row(rl, R64_PA_LAYOUT) + tl), par_o = 8 * r64::pa_row(lane, R64_PA_LAYOUT);
+#if R64_PA_LAYOUT
+  asm volatile("" : "+v"(paw_o), "+v"(par_o));
+#endif
+  double* const paw = reinterpret_cast<double*>(reinterpret_cast<char*>(pa) + paw_o);
   double* const sb = &sm.u.l.sb[0][0];
+  // the lane's sb addresses (rows64_layout.h), set once per document: where it stores its topic pair's wave
+  // sums (topic 2·rl + 1's slot is 2·rl's + kSbPitch: sb_pair_adjacent) and the two 16-byte halves of its ψ
+  // topic's record in the order it reads them.  With the swizzle they are laundered, so each is one register
+  // held across the loop and not re-formed from w and the lane maps inside it.
+  // (byte offsets: sb's own offset stays the instructions' immediate)
+  int sbw_o = 8 * r64::sb_slot(KL, tl, 2 * rl, w, R64_SB_SWZ);
+  int sp0_o = 8 * (tt * kSbPitch + 2 * r64::sb_read_first(tt, R64_SB_SWZ));
+  int sp1_o = 8 * (tt * kSbPitch + 2 * (r64::sb_read_first(tt, R64_SB_SWZ) ^ 1));
+#if R64_SB_SWZ
+  asm volatile("" : "+v"(sbw_o), "+v"(sp0_o), "+v"(sp1_o));
+#endif
+  [[maybe_unused]] double* const sbw = reinterpret_cast<double*>(reinterpret_cast<char*>(sb) + sbw_o);
+  const double2* const sp0 = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(sb) + sp0_o);
+  const double2* const sp1 = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(sb) + sp1_o);
+  double* const esw = &sm.esum[w];  // the wave's Σ r·ε' slot
   const PsiExpK expk = psi_expk_load(sm.psik);
   double rr[R];
   double qr = 0.0;  // worker: r of its row (φ without ε' in qdt)
@@ -409,7 +441,7 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
     __builtin_amdgcn_wave_barrier();
     if (R64_PRIO >= 2) __builtin_amdgcn_s_setprio(3);
     if (lane < 8 * R) {
-      const double2* const pr = reinterpret_cast<const double2*>(pa + lane * kPaPitch);
+      const double2* const pr = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(pa) + par_o);
       const double2 x0 = pr[0], x1 = pr[1], x2 = pr[2], x3 = pr[3];
       qdt = ((x0.x + x0.y) + (x1.x + x1.y)) + ((x2.x + x2.y) + (x3.x + x3.y));
       const double ph = fma(qe2, 0x1p-53, qdt);
@@ -427,9 +459,9 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
 #endif
     if (__builtin_amdgcn_ballot_w64(live) != 0) {
       const double e = wave_sum_d(lane < 8 * R ? qr * (qe2 * 0x1p-53) : 0.0);
-      if (lane == 0) sm.esum[w] = e;
+      if (lane == 0) *esw = e;
     } else if (lane == 0) {
-      sm.esum[w] = 0.0;
+      *esw = 0.0;
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -490,8 +522,8 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
       }
       double s0, s1;
       rs_rows8(x, lane, s0, s1);
-      if (2 * rl < KL) sb[(KL * tl + 2 * rl) * kSbPitch + w] = s0;
-      if (2 * rl + 1 < KL) sb[(KL * tl + 2 * rl + 1) * kSbPitch + w] = s1;
+      if (2 * rl < KL) sbw[0] = s0;
+      if (2 * rl + 1 < KL) sbw[kSbPitch] = s1;
     }
 #endif
     STAMP(3);  // s FMAs + partial stores
@@ -503,8 +535,7 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
       double dg = 0.0;
       if (town) {
         // every LDS read of the phase issued together: the partials, γ, eθ, the four ε' sums
-        const double2* const sp = reinterpret_cast<const double2*>(sb + tt * kSbPitch);
-        const double2 x0 = sp[0], x1 = sp[1];  // the four waves' sums
+        const double2 x0 = *sp0, x1 = *sp1;  // the four waves' sums (the halves in either order: the same sum)
         const double g = mir ? gm : sm.gam[tt], eo = sm.eth[ttl][ttp];
         const double2 ap = *reinterpret_cast<const double2*>(&sm.apc[tt][0]);  // α_t, ψc_t
         const double2 e01 = *reinterpret_cast<const double2*>(&sm.esum[0]);
@@ -531,9 +562,8 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
       // wave's: same partials, same order), and Σ|Δγ| — its six-step reduction no longer sits on the ψ chain
       double dg = 0.0;
       if (town) {
-        const double2* const sp = reinterpret_cast<const double2*>(sb + tt * kSbPitch);
         const double al = sm.apc[tt][0];
-        const double2 y0 = sp[0], y1 = sp[1];
+        const double2 y0 = *sp0, y1 = *sp1;
         const double s = (y0.x + y0.y) + (y1.x + y1.y);
         const double gn = fma(em, s, al);
         dg = fabs(gn - gm);

@@ -7,7 +7,7 @@
 #   check              pytest -m gpu (PYTEST_K / TESTS narrow it) + smoke
 #   bench              the full bench line (python bench.py --full) → bench.json beside the logs
 #   ab                 headline + planted lines of the in-tree library and of each LIBS variant
-#                      (libstc_<n>.so); DTYPE=f32 for the fp32 kernels
+#                      (libstc_<n>.so); DTYPE=f32 for the fp32 kernels; ROUNDS=n interleaves n rounds
 #   configs            BASELINE configs 4 / 5 lines, fp64 + fp32, with the CPU baseline (DTYPES narrows)
 #   c4ab / c5ab        config 4 / 5 A/B of the LIBS variants against the in-tree library (STEPS, WARMUP)
 #   c2env/c4env/c5env  config 2 / 4 / 5 lines of the in-tree library under each ENVS="name:VAR=val,…" setting
@@ -15,7 +15,8 @@
 #   prof               rocprofv3 stats + PMC passes of WORKLOADS="name:bench args;…" (each into
 #                      gpurun_out/prof_<name>; summarise with tools/pmc_summary.py --steady)
 #   bitwise            tools/ab_bitwise.py: each LIBS variant's E-step / next() outputs vs the in-tree library's
-#   counters           one --pmc pass of $COUNTERS (those this rocprofv3 lists) over the headline E-step
+#   counters           one --pmc pass of $COUNTERS (those this rocprofv3 lists) over the headline E-step, of the
+#                      in-tree library and of each LIBS variant
 #   ubench             tools/ubench_f64 (the fp64 chain micro-benchmark)
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
@@ -46,11 +47,15 @@ r_bench() {
 }
 r_ab() {
   local B="python bench.py --steps ${STEPS:-10} --warmup ${WARMUP:-5} $FAST --dtype ${DTYPE:-f64}"
-  step b_new 300 $B
-  step p_new 300 $B $PLANTED
-  for n in $LIBS; do
-    step b_$n 300 env STC_LIB=$(lib $n) $B
-    step p_$n 300 env STC_LIB=$(lib $n) $B $PLANTED
+  local r s
+  for r in $(seq 1 ${ROUNDS:-1}); do  # ROUNDS > 1: the builds interleaved, logs suffixed _r<round>
+    [ ${ROUNDS:-1} -gt 1 ] && s=_r$r || s=
+    step b_new$s 300 $B
+    step p_new$s 300 $B $PLANTED
+    for n in $LIBS; do
+      step b_$n$s 300 env STC_LIB=$(lib $n) $B
+      step p_$n$s 300 env STC_LIB=$(lib $n) $B $PLANTED
+    done
   done
 }
 r_configs() {
@@ -114,6 +119,11 @@ print(" ".join(w for w in sys.argv[1].split() if re.search(r"\b%s\b" % re.escape
   [ -n "$C" ] || { echo "none of $COUNTERS listed" >> gpurun_out/status.log; return 0; }
   step counters 400 rocprofv3 --pmc $C --kernel-include-regex "${KREGEX:-k_estep}" -d $out/p -o p --output-format csv -- \
     python3 bench.py --steps 3 --warmup 1 $FAST --workers 1 ${BENCH_ARGS:-}
+  local n
+  for n in $LIBS; do  # the same pass over each LIBS variant, into counters/p_<n>
+    step counters_$n 400 env STC_LIB=$(lib $n) rocprofv3 --pmc $C --kernel-include-regex "${KREGEX:-k_estep}" -d $out/p_$n \
+      -o p --output-format csv -- python3 bench.py --steps 3 --warmup 1 $FAST --workers 1 ${BENCH_ARGS:-}
+  done
 }
 r_ubench() { step ubench 120 ./tools/ubench_f64; }
 
