@@ -9,6 +9,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 #include <memory>
 #include <type_traits>
@@ -50,28 +51,21 @@ struct stc_lda {
   int P64 = 0, lds_rows64 = 0;  // the fp64 workgroup kernel's LDS pitch / rows at this kp
   int64_t cap64 = 0;            // the fp64 fast kernels' row capacity (longer documents: the workgroup kernel)
   DevBuf Bp64, vals32, m_batch, m_orig, m_bptr, m_slot, m_cnt, eth64, elogth64, r64, keys64, vals64, gamma64, g0_64;
-  const DCsr* vals32_for = nullptr;
-  int32_t* hmcnt = nullptr;     // pinned: the two list counts
   DevBuf s_counts, s_weights, s_short, s_cincl, s_wincl, s_sincl;
   // the next draw is sampled on a side stream, concurrently with this step's E-step (it reads only
   // indptr and writes only the s_* buffers, which this step's fill_batch has consumed)
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fill = nullptr, ev_samp = nullptr;
   bool samp_pending = false;
   // next(): the prefetched draw's batch (fill, slot order, offsets) is built on the side stream once the
   // previous step's E-step has read the batch buffers (ev_est), under that step's M-step and all-gathers.
   // prep_side: the last user of the batch buffers was next() (any other call's ensure_batch clears it).
-  hipEvent_t ev_est = nullptr;
   bool prep_side = false;
   DevBuf side_scan_tmp;
   DevBuf long_list;  // rows / grid kernels: the launch's long documents (count word + slot offsets)
   DevBuf o_keys, o_keys2, o_idx, o_idx2, o_batch, o_orig, o_nnz, o_tmp;  // slot ordering (order_slots)
   bool sort_docs = true;  // STC_SORT_DOCS=0 keeps sampling order
-  // fp64 rows kernels: the sstats pairs built and radix-sorted on a low-priority stream beside the E-step
-  // (estep_and_stats); STC_PRESORT=0 sorts them after the E-step
-  int presort = 1;
-  hipStream_t sort_stream = nullptr;
-  hipEvent_t ev_ps0 = nullptr, ev_sorted = nullptr;
+  // fp64 rows kernels: the sstats pairs built and radix-sorted beside the E-step (estep_and_stats), on the side
+  // stream when the handle has one, else on sort_stream; STC_PRESORT=0 sorts them after the E-step
+  bool presort = true;
   // many-topic kernel: per-entry row order, rarest terms first (lda_wide.hip), for `order_for`
   DevBuf order, order_df;
   const DCsr* order_for = nullptr;
@@ -83,8 +77,6 @@ struct stc_lda {
   bool tgrid = true;  // fp64 many-topic documents: the topic-split grid team kernel when they fit (STC_TGRID=0: off)
   bool tgrid_require = false;  // STC_TGRID=2 (tests): a many-topic fp64 launch that cannot take it is an error
   DevBuf team_words, team_x;
-  unsigned* htmo = nullptr;  // pinned copy of the team kernel's timeout word
-  int64_t team_fallbacks = 0;  // team launches re-run on the one-CU kernel after a timeout
   int64_t kcount[STC_KC_N] = {};  // E-step launches per kernel family (stc_lda_kernel_counts)
 
   // M-step sharding over the vocabulary (multi-GPU): rank r owns λ / expElogβ rows [r·Vs, (r+1)·Vs);
@@ -98,8 +90,6 @@ struct stc_lda {
   // its sstats launch is done, and the M-step of sub-chunk j under the reduce-scatter of j+1
   // (STC_RS_CHUNKS, 1: one reduce-scatter after the whole stat)
   int rs_chunks = 4;
-  hipStream_t cstream = nullptr;
-  hipEvent_t ev_ss[16] = {}, ev_rs[16] = {};
   int64_t Vs = 0, vpad = 0;
   // one rank: sstats stamps the rows it writes (rowstamp[v] = the step's id) and the M-step reads the other
   // rows as zero, so stat is not cleared every step (V·kp·T bytes: 4.2 GB at config 5)
@@ -114,42 +104,31 @@ struct stc_lda {
   // this step's collective, so the next call waits on an event instead of draining the stream
   bool pre_valid = false, pre_inflight = false;
   int64_t pre_draw = 0;
-  hipEvent_t ev_pre = nullptr;
-  int64_t* hpre = nullptr;
 
   bool timing = false;
-  hipEvent_t ev[3][6] = {};
   int ev_set = 0;
   bool ev_pending[3] = {false, false, false};
   double acc_ms[5] = {0, 0, 0, 0, 0};
   int64_t timed_steps = 0;
   int64_t cum_docs = 0, cum_entries = 0;
 
-  int64_t* hcnt = nullptr;  // pinned host words for the per-step count readback (one small copy)
   DevBuf dcnt;
 
-  ~stc_lda() {
-    for (auto& s : ev)
-      for (auto& e : s)
-        if (e) (void)hipEventDestroy(e);
-    if (hcnt) (void)hipHostFree(hcnt);
-    if (hmcnt) (void)hipHostFree(hmcnt);
-    if (hpre) (void)hipHostFree(hpre);
-    if (htmo) (void)hipHostFree(htmo);
-    if (ev_pre) (void)hipEventDestroy(ev_pre);
-    if (ev_fill) (void)hipEventDestroy(ev_fill);
-    if (ev_samp) (void)hipEventDestroy(ev_samp);
-    if (ev_est) (void)hipEventDestroy(ev_est);
-    if (side) (void)hipStreamDestroy(side);
-    for (int j = 0; j < 16; ++j) {
-      if (ev_ss[j]) (void)hipEventDestroy(ev_ss[j]);
-      if (ev_rs[j]) (void)hipEventDestroy(ev_rs[j]);
-    }
-    if (cstream) (void)hipStreamDestroy(cstream);
-    if (ev_ps0) (void)hipEventDestroy(ev_ps0);
-    if (ev_sorted) (void)hipEventDestroy(ev_sorted);
-    if (sort_stream) (void)hipStreamDestroy(sort_stream);
-  }
+  // The streams, events and pinned host words, each made on first use (stc_handles.h).  Members are released
+  // last-declared first, so these, declared after every DevBuf, go before the buffers are freed: the timing
+  // events, the pinned words, then each stream after its events.  stc_lda_destroy drains the main stream, side
+  // and cstream first; sort_stream needs no drain, because every call that uses it makes the main stream wait
+  // for ev_sorted before it returns, so the drained main stream has seen the sort's end.
+  Stream sort_stream;  // lowest priority; made when the presort runs on a handle that has no side stream
+  Event ev_sorted, ev_ps0;
+  Stream cstream;  // made by the first chunked sharded tail
+  Event ev_rs[16], ev_ss[16];
+  Stream side;  // made by the first next()
+  Event ev_est, ev_samp, ev_fill, ev_pre;
+  Pinned<unsigned> htmo;          // the team kernel's timeout word
+  Pinned<int64_t, 4> hpre, hcnt;  // a draw's (n, E, n_short, global n): prefetched / read synchronously
+  Pinned<int32_t, 2> hmcnt;       // mixed_resolve's two list counts
+  Event ev[3][6];                 // phase timing (made in stc_lda_create, timing on)
 };
 
 // ---- what stc_group reads and sets of its members (lda_online.h) ----
@@ -163,7 +142,7 @@ void stc::forget_corpus(stc_lda& L) {
   L.order_for = nullptr;
   L.pre_valid = false;
 }
-hipStream_t stc::side_stream(const stc_lda& L) { return L.side; }
+hipStream_t stc::side_stream(const stc_lda& L) { return L.side.s; }
 // the CSR value dtype a handle reads (a mixed handle: the fp64 values, and an fp32 copy it makes itself)
 int stc::corpus_dtype(const stc_lda& L) { return L.mixed ? STC_F64 : L.dtype; }
 // A call that failed after queuing the next draw on the side stream (before train_tail ordered the main
@@ -172,7 +151,7 @@ int stc::corpus_dtype(const stc_lda& L) { return L.mixed ? STC_F64 : L.dtype; }
 void stc::settle_side(stc_lda& L) {
   if (!L.samp_pending) return;
   L.ctx->use();
-  wait_stream(*L.ctx, L.side);
+  wait_stream(*L.ctx, L.side.s);
   L.samp_pending = false;
   L.pre_inflight = false;
   L.pre_valid = false;
@@ -222,16 +201,16 @@ inline int bits_for(int64_t n) {
 }
 
 void record(stc_lda& L, int slot) {
-  if (L.timing) HIP_CHECK(hipEventRecord(L.ev[L.ev_set][slot], L.ctx->stream));
+  if (L.timing) HIP_CHECK(hipEventRecord(L.ev[L.ev_set][slot].e, L.ctx->stream));
 }
 
 // add the phase times of an event set whose step has completed (left pending otherwise)
 void harvest(stc_lda& L, int set) {
   if (!L.ev_pending[set]) return;
-  if (hipEventQuery(L.ev[set][5]) != hipSuccess) return;
+  if (hipEventQuery(L.ev[set][5].e) != hipSuccess) return;
   for (int p = 0; p < 5; ++p) {
     float ms = 0.f;
-    HIP_CHECK(hipEventElapsedTime(&ms, L.ev[set][p], L.ev[set][p + 1]));
+    HIP_CHECK(hipEventElapsedTime(&ms, L.ev[set][p].e, L.ev[set][p + 1].e));
     L.acc_ms[p] += ms;
   }
   L.timed_steps += 1;
@@ -243,7 +222,7 @@ void harvest_all(stc_lda& L) {
 // before a step records into the current set: a set is reused three steps later, long complete
 void claim_event_set(stc_lda& L) {
   if (!L.timing || !L.ev_pending[L.ev_set]) return;
-  wait_event(*L.ctx, L.ev[L.ev_set][5]);
+  wait_event(*L.ctx, L.ev[L.ev_set][5].e);
   harvest(L, L.ev_set);
 }
 
@@ -404,8 +383,10 @@ lda::EStepArgs<T> estep_args(stc_lda& L) {
 }
 
 // the register-resident kernel for the (k, dtype): the grid kernels up to k = 128 (fp32) / 104 (fp64),
-// the topics-across-lanes kernel (lda_wide.hip) beyond
-bool use_wide(int k, int dtype) { return dtype == STC_F32 ? lda::grid_row_cap(k) == 0 : lda::rows64_row_cap(k) == 0; }
+// the topics-across-lanes kernel (lda_wide.hip) beyond; fast_row_cap: the longest document that kernel takes
+int grid_family_cap(int k, int dtype) { return dtype == STC_F32 ? lda::grid_row_cap(k) : lda::rows64_row_cap(k); }
+bool use_wide(int k, int dtype) { return grid_family_cap(k, dtype) == 0; }
+int fast_row_cap(int k, int dtype) { return use_wide(k, dtype) ? lda::wide_row_cap(k) : grid_family_cap(k, dtype); }
 
 // the fast kernel's slots [0, n_short) in descending nnz: the longest documents start first, so the
 // launch does not end on a few long documents started late (longest-processing-time-first).  Each
@@ -497,8 +478,7 @@ TeamChoice team_choice(const stc_lda& L, double mean_rows, int64_t max_row) {
 // (which every member of a group or every rank gets on its own, so no rank's state can diverge).
 // debug knob STC_TEAM_FAULT=m: member m of team 0 never publishes (its partners time out quickly)
 int team_fault_member() {
-  const char* e = getenv("STC_TEAM_FAULT");
-  return e ? atoi(e) : -1;
+  return env_int("STC_TEAM_FAULT", -1, INT_MIN, INT_MAX);
 }
 
 template <typename T>
@@ -518,10 +498,6 @@ bool launch_wide_team(stc_lda& L, const lda::EStepArgs<T>& w, bool stats, TeamCh
   const size_t xbytes = 16 * (size_t)teams * 2 * P * (size_t)wt.xstride;
   L.team_words.reserve(16);
   L.team_x.reserve(xbytes);
-  if (!L.htmo) {
-    HIP_CHECK(hipHostMalloc((void**)&L.htmo, sizeof(unsigned), hipHostMallocDefault));
-    *L.htmo = 0;
-  }
   wt.tmo = L.team_words.as<unsigned>();
   wt.xbuf = L.team_x.p;
   wt.fault_member = team_fault_member();
@@ -538,7 +514,7 @@ bool launch_wide_team(stc_lda& L, const lda::EStepArgs<T>& w, bool stats, TeamCh
   } else {
     ok = tc.topics ? lda::launch_estep_wide_tc<T>(s, w, stats, wt) : lda::launch_estep_wide_mc<T>(s, w, stats, wt);
   }
-  if (ok) HIP_CHECK(hipMemcpyAsync(L.htmo, wt.tmo, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  if (ok) HIP_CHECK(hipMemcpyAsync(L.htmo.get(), wt.tmo, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   if (!ok && tc.grid && L.tgrid_require) throw Error(STC_ERR_STATE, "STC_TGRID=2: the grid team could not be resident");
   return ok;
 }
@@ -559,9 +535,8 @@ void launch_split(stc_lda& L, const DCsr& m, lda::EStepArgs<T> a, int64_t n, int
     if (team) {  // launched (a grid that could not be resident falls through to the one-CU kernel)
       L.kcount[tc.grid ? STC_KC_TGRID64 : tc.topics ? STC_KC_WIDE_TC : STC_KC_WIDE_MC] += 1;
       wait_stream(*L.ctx, s);
-      if (*L.htmo) {  // a team gave up: the same slots on the one-CU kernel (it rewrites every output)
-        *L.htmo = 0;
-        L.team_fallbacks += 1;
+      if (*L.htmo.get()) {  // a team gave up: the same slots on the one-CU kernel (it rewrites every output)
+        *L.htmo.get() = 0;
         L.kcount[STC_KC_TEAM_FALLBACK] += 1;
         L.kcount[STC_KC_WIDE] += 1;
         lda::launch_estep_wide<T>(s, w, stats, bound);
@@ -569,21 +544,16 @@ void launch_split(stc_lda& L, const DCsr& m, lda::EStepArgs<T> a, int64_t n, int
     } else if (use_wide(L.k, dt)) {
       L.kcount[STC_KC_WIDE] += 1;
       lda::launch_estep_wide<T>(s, w, stats, bound);
-    } else if constexpr (std::is_same<T, float>::value) {
-      const bool long_docs = m.max_row < 0 || m.max_row > lda::grid_onchip_rows(L.k);
+    } else {  // the dtype's grid family: fp32 grid, fp64 rows64 (which counts its long-document pass)
+      constexpr bool f32 = std::is_same<T, float>::value;
+      const bool long_docs = m.max_row < 0 || m.max_row > (f32 ? lda::grid_onchip_rows(L.k) : lda::rows64_onchip_rows(L.k));
       // the long-document list (count word + slots) and, past it, the resident grid's ticket word
       L.long_list.reserve(4 * (size_t)(n_short + 2));
       w.long_list = L.long_list.as<int32_t>();
-      L.kcount[STC_KC_GRID] += 1;
-      lda::launch_estep_grid(s, w, stats, bound, long_docs);
-    } else {
-      const bool long_docs = m.max_row < 0 || m.max_row > lda::rows64_onchip_rows(L.k);
-      // the long-document list (count word + slots) and, past it, the resident grid's ticket word
-      L.long_list.reserve(4 * (size_t)(n_short + 2));
-      w.long_list = L.long_list.as<int32_t>();
-      L.kcount[STC_KC_ROWS64] += 1;
-      if (long_docs) L.kcount[STC_KC_ROWS64_LONG] += 1;
-      lda::launch_estep_rows64(s, w, stats, bound, long_docs);
+      L.kcount[f32 ? STC_KC_GRID : STC_KC_ROWS64] += 1;
+      if (!f32 && long_docs) L.kcount[STC_KC_ROWS64_LONG] += 1;
+      if constexpr (f32) lda::launch_estep_grid(s, w, stats, bound, long_docs);
+      else lda::launch_estep_rows64(s, w, stats, bound, long_docs);
     }
   }
   if (n > n_short) {
@@ -666,14 +636,14 @@ void mixed_resolve(stc_lda& L, int64_t n, int64_t E, int64_t iteration, const do
   L.m_slot.reserve(4 * n);
   L.m_bptr.reserve(8 * n);
   L.m_cnt.reserve(2 * sizeof(int32_t));
-  if (!L.hmcnt) HIP_CHECK(hipHostMalloc((void**)&L.hmcnt, 2 * sizeof(int32_t), hipHostMallocDefault));
+  int32_t* hm = L.hmcnt.get();
   lda::launch_mixed_list(s, m.indptr.as<int64_t>(), L.batch.as<int32_t>(), L.orig.as<int32_t>(), L.bptr.as<int64_t>(),
                          L.iters.as<int32_t>(), L.nonempty.as<int32_t>(), n, L.mixed_thr, L.cap64,
                          L.m_batch.as<int32_t>(), L.m_orig.as<int32_t>(), L.m_bptr.as<int64_t>(), L.m_slot.as<int32_t>(),
                          L.m_cnt.as<int32_t>());
-  HIP_CHECK(hipMemcpyAsync(L.hmcnt, L.m_cnt.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(hm, L.m_cnt.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   wait_stream(*L.ctx, s);
-  const int ms = L.hmcnt[0], ml = L.hmcnt[1];
+  const int ms = hm[0], ml = hm[1];
   if (ms + ml == 0) return;
   L.kcount[STC_KC_MIXED_RESOLVES] += 1;
   L.kcount[STC_KC_MIXED_DOCS] += ms + ml;
@@ -754,48 +724,35 @@ void estep_and_stats(stc_lda& L, int64_t n, int64_t n_short, int64_t E, const T*
   a.nonempty = L.nonempty.as<int32_t>();
   record(L, 1);
   // fp64 on the rows kernels (k ≤ 104, every slot on them): an entry's sort value carries its index, not r, so
-  // the (term, slot) pairs and their radix sort depend on the batch alone — they run on a low-priority stream
-  // beside the E-step, whose blocks take the CU slots the resident grid frees as it drains, instead of after it
+  // the (term, slot) pairs and their radix sort depend on the batch alone — they run on another stream beside the
+  // E-step, whose blocks take the CU slots the resident grid frees as it drains, instead of after it
   bool presort = false;
   if constexpr (std::is_same<T, double>::value)
     presort = L.presort && !L.mixed && !use_wide(L.k, STC_F64) && n_short == n && E > 0;
-  hipStream_t ss = nullptr;  // the handle's side stream when it has one (no extra hardware queue), else its own
-  auto enqueue_presort = [&] {
+  hipStream_t ss = nullptr;
+  if (presort) {
+    // a process with several handles runs past the device's hardware queues (GPU_MAX_HW_QUEUES) when each adds
+    // a stream, and a stream sharing a queue waits behind unrelated work: the side stream (next()'s draws,
+    // which then queue behind the sort) is used when it exists, else a lowest-priority stream of the sort's own
+    ss = L.side.s ? L.side.s : L.sort_stream.get(hipStreamNonBlocking, true);
+    HIP_CHECK(hipEventRecord(L.ev_ps0.get(), s));  // the batch and its entry offsets are built; skeys / svals free
+    HIP_CHECK(hipStreamWaitEvent(ss, L.ev_ps0.get(), 0));
+    a.keys = nullptr;  // (the E-step kernels leave the pairs alone)
+    a.vals = nullptr;
+  }
+  launch_split<T>(L, *L.corpus, a, n, n_short, true, false, n > 0 ? (double)E / (double)n : 0.0);
+  if (presort) {  // enqueued after the E-step launch, so the resident grid is dispatched first
     lda::launch_entry_pairs(ss, L.corpus->indptr.as<int64_t>(), L.corpus->indices.as<int32_t>(),
                             L.batch.as<int32_t>(), L.bptr.as<int64_t>(), n, L.keys.as<uint32_t>(), L.vals.as<uint64_t>());
     size_t tb = L.sort_tmp.bytes;
     HIP_CHECK(term_sort(L.sort_tmp.p, tb, L.keys.as<uint32_t>(), L.skeys.as<uint32_t>(), L.vals.as<uint64_t>(),
                         L.svals.as<uint64_t>(), E, bits_for(L.V), ss));
-    HIP_CHECK(hipEventRecord(L.ev_sorted, ss));
-  };
-  if (presort) {
-    if (!L.ev_ps0) {
-      HIP_CHECK(hipEventCreateWithFlags(&L.ev_ps0, hipEventDisableTiming));
-      HIP_CHECK(hipEventCreateWithFlags(&L.ev_sorted, hipEventDisableTiming));
-    }
-    // a process with several handles runs past the device's hardware queues (GPU_MAX_HW_QUEUES) when each adds
-    // a stream, and a stream sharing a queue waits behind unrelated work: the side stream (next()'s draws,
-    // which then queue behind the sort) is used when it exists
-    if (!L.side && !L.sort_stream) {
-      int least = 0, greatest = 0;
-      HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-      HIP_CHECK(hipStreamCreateWithPriority(&L.sort_stream, hipStreamNonBlocking, least));
-    }
-    ss = L.side ? L.side : L.sort_stream;
-    HIP_CHECK(hipEventRecord(L.ev_ps0, s));  // the batch and its entry offsets are built; skeys / svals free
-    HIP_CHECK(hipStreamWaitEvent(ss, L.ev_ps0, 0));
-    // STC_PRESORT=2: the pairs and the sort enqueued before the E-step launch (their blocks then compete with
-    // the grid's first workgroups); default: after it, so the resident grid is dispatched first
-    if (L.presort == 2) enqueue_presort();
-    a.keys = nullptr;  // (the E-step kernels leave the pairs alone)
-    a.vals = nullptr;
+    HIP_CHECK(hipEventRecord(L.ev_sorted.get(), ss));
   }
-  launch_split<T>(L, *L.corpus, a, n, n_short, true, false, n > 0 ? (double)E / (double)n : 0.0);
-  if (presort && L.presort != 2) enqueue_presort();
   if constexpr (std::is_same<T, float>::value) {
     if (L.mixed) mixed_resolve(L, n, E, iteration, g0_64, want_gamma);
   }
-  if (L.ev_est) HIP_CHECK(hipEventRecord(L.ev_est, s));  // the batch buffers are free (next_impl)
+  if (L.ev_est.e) HIP_CHECK(hipEventRecord(L.ev_est.e, s));  // the batch buffers are free (next_impl)
   record(L, 2);
   // logphat first: its all-reduce rides with the first stat sub-chunk of a sharded step
   if (n > 0) {
@@ -817,7 +774,7 @@ void estep_and_stats(stc_lda& L, int64_t n, int64_t n_short, int64_t E, const T*
     HIP_CHECK(hipMemsetAsync(L.stat.p, 0, sizeof(T) * L.vpad * L.kp, s));  // padded rows stay zero
   }
   if (presort) {
-    HIP_CHECK(hipStreamWaitEvent(s, L.ev_sorted, 0));
+    HIP_CHECK(hipStreamWaitEvent(s, L.ev_sorted.e, 0));
   } else if (E > 0) {
     size_t tb = L.sort_tmp.bytes;
     HIP_CHECK(term_sort(L.sort_tmp.p, tb, L.keys.as<uint32_t>(), L.skeys.as<uint32_t>(), L.vals.as<uint64_t>(),
@@ -834,8 +791,7 @@ void estep_and_stats(stc_lda& L, int64_t n, int64_t n_short, int64_t E, const T*
       m.sub = j;
       lda::launch_sstats<T>(s, L.skeys.as<uint32_t>(), L.svals.as<uint64_t>(), E, L.r.as<T>(), L.eth.as<T>(),
                             L.kp, L.stat.as<T>(), L.headbuf.as<T>(), L.tailbuf.as<T>(), m);
-      if (!L.ev_ss[j]) HIP_CHECK(hipEventCreateWithFlags(&L.ev_ss[j], hipEventDisableTiming));
-      HIP_CHECK(hipEventRecord(L.ev_ss[j], s));
+      HIP_CHECK(hipEventRecord(L.ev_ss[j].get(), s));
     }
   }
   record(L, 3);
@@ -867,130 +823,33 @@ void mstep_sub(stc_lda& L, const lda::StatMap& m, int r, int j, double rho, doub
                             w / lda::kRowsPerBlock, L.mixed ? L.Bp64.as<double>() + v0 * L.kp : nullptr);
 }
 
-// [U] submitMiniBatch tail: the stats merge (treeReduce ≙ RCCL), updateLambda, updateAlpha.
-//  * one GPU: the fused λ update + expElogβ' pass over all rows, then colsum and ψ(colsum).
-//  * N ranks: reduce-scatter of stat (each rank receives the summed rows of its vocabulary slice) and
-//    the logphat / count all-reduce in one group; the slice's fused λ update + expElogβ' pass; ONE
-//    group of all-gathers — the per-block colsum partials (k doubles per 64 rows), expElogβ' and
-//    logscale — then colsum reduced in the one-GPU block order, so it is identical on every rank.
-//    λ stays sharded (lam_stale) until a reader gathers it.  Per rank: stat (N−1)/N·V·kp·T bytes
-//    out, expElogβ' the same in, against 2(N−1)/N for an all-reduce, and 1/N of the M-step work.
-template <typename T>
-void train_tail_split(stc_lda& L, const lda::StatMap& lay, bool had_samp, int64_t n, int64_t E,
-                      stc_step_stats* st);
-template <typename T>
-void train_finish(stc_lda& L, int64_t n, int64_t E, stc_step_stats* st);
-
-//  * N ranks with rs_chunks > 1 (stat_layout: nsub sub-chunks): sstats ran once per sub-chunk
-//    (estep_and_stats split) and recorded ev_ss[j]; the reduce-scatter of sub-chunk j (one contiguous
-//    buffer in that layout) runs on cstream as soon as ev_ss[j] fires — under the sstats launches of
-//    j+1… — with the logphat / count all-reduce in sub-chunk 0's group, and the main stream runs the
-//    M-step of sub-chunk j under the reduce-scatter of j+1.  Each element is summed over the same
-//    ranks in the same way as by the single reduce-scatter, and sstats builds every row exactly as
-//    the single launch does, so the result is the unchunked step's.
-template <typename T>
-void train_tail(stc_lda& L, int64_t n, int64_t E, stc_step_stats* st) {
-  Ctx& c = *L.ctx;
-  hipStream_t s = c.stream;
-  const bool ranks = sharded(L);
-  const lda::StatMap lay = stat_layout(L);
-  if (L.tail_fault > 0 && --L.tail_fault == 0) {
-    throw Error(STC_ERR_STATE, "injected member failure between sstats and the reduce-scatter (STC_GROUP_STEP_FAULT)");
-  }
-  const bool had_samp = L.samp_pending;
-  if (L.samp_pending) {  // the next draw's counts (side stream) feed this step's collective / readback
-    HIP_CHECK(hipStreamWaitEvent(s, L.ev_samp, 0));
-    L.samp_pending = false;
-  }
-  if (ranks && lay.nsub > 1) {
-    train_tail_split<T>(L, lay, had_samp, n, E, st);
-    return;
-  }
-  if (c.coll()) {
-    coll_group_start(c);
-    if (ranks) {
-      const size_t cnt = (size_t)(L.Vs * L.kp);
-      coll_reduce_scatter(c, L.stat.p, L.stat.as<T>() + (size_t)c.rank * cnt, cnt, RcclType<T>::v, s);
-    }
-    coll_all_reduce(c, L.small.p, (size_t)(L.k + 1), ncclFloat64, s);
-    if (L.pre_inflight)  // the next draw's global batch size (word 3), for the next call
-      coll_all_reduce(c, L.dcnt.as<int64_t>() + 3, 1, ncclInt64, s);
-    coll_group_end(c);
-  }
-  if (L.pre_inflight) {
-    HIP_CHECK(hipMemcpyAsync(L.hpre, L.dcnt.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipEventRecord(L.ev_pre, s));
-    L.pre_inflight = false;
-    L.pre_valid = true;
-  }
-  record(L, 4);
-  L.iteration += 1;
-  const double rho = std::pow(L.cfg.tau0 + (double)L.iteration, -L.cfg.kappa);
+// ---- what the two tails below share ----
+// the step's learning rate ρ_t, the corpus / batch scale and the device word that gates an empty batch
+// (L.iteration: already this step's)
+struct StepRates {
+  double rho, scale;
+  const double* gate;
+};
+StepRates step_rates(const stc_lda& L) {
   const double batch_size = std::ceil(L.cfg.mini_batch_fraction * (double)L.corpus_total);
-  const double scale = (double)L.corpus_total / batch_size;
-  const double* gate = L.small.as<double>() + L.k;
-  const int64_t nb_all = L.shards * (L.Vs / lda::kRowsPerBlock);
-  if (ranks) {
-    const size_t nbs = (size_t)(L.Vs / lda::kRowsPerBlock);
-    mstep_slice<T>(L, c.rank, rho, scale, gate);
-    const size_t cnt = (size_t)(L.Vs * L.kp);
-    coll_group_start(c);
-    coll_all_gather(c, L.colpart.as<double>() + (size_t)c.rank * nbs * L.k, L.colpart.p, nbs * L.k, ncclFloat64, s);
-    coll_all_gather(c, L.Bp.as<T>() + (size_t)c.rank * cnt, L.Bp.p, cnt, RcclType<T>::v, s);
-    if (L.mixed) coll_all_gather(c, L.Bp64.as<double>() + (size_t)c.rank * cnt, L.Bp64.p, cnt, ncclFloat64, s);
-    coll_all_gather(c, L.logscale.as<double>() + (size_t)c.rank * L.Vs, L.logscale.p, (size_t)L.Vs, ncclFloat64, s);
-    coll_group_end(c);
-    lda::launch_colsum_reduce(s, L.colpart.as<double>(), nb_all, L.k, gate, L.colsum.as<double>(),
-                              L.psic.as<double>());
-    L.lam_stale = true;
-  } else {  // one GPU: all slices here (one unless STC_VIRTUAL_SHARDS)
-    for (int r = 0; r < L.shards; ++r) mstep_slice<T>(L, r, rho, scale, gate);
-    lda::launch_colsum_reduce(s, L.colpart.as<double>(), nb_all, L.k, gate, L.colsum.as<double>(),
-                              L.psic.as<double>());
-  }
-  if (L.cfg.optimize_doc_concentration)
-    lda::launch_update_alpha(s, L.alpha.as<double>(), L.small.as<double>(), L.k, rho);
-  train_finish<T>(L, n, E, st);
+  return {std::pow(L.cfg.tau0 + (double)L.iteration, -L.cfg.kappa), (double)L.corpus_total / batch_size,
+          L.small.as<double>() + L.k};
 }
 
+// the prefetched draw's counts (dcnt; word 3 = its global size once stream q's work is done) to the host:
+// the next call waits for ev_pre instead of draining a stream
+void publish_draw(stc_lda& L, hipStream_t q) {
+  HIP_CHECK(hipMemcpyAsync(L.hpre.get(), L.dcnt.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, q));
+  HIP_CHECK(hipEventRecord(L.ev_pre.get(), q));
+  L.pre_inflight = false;
+  L.pre_valid = true;
+}
+
+// after a rank's slice update: the group of all-gathers and the colsum reduce (train_tail's comment)
 template <typename T>
-void train_tail_split(stc_lda& L, const lda::StatMap& lay, bool had_samp, int64_t n, int64_t E,
-                      stc_step_stats* st) {
+void gather_slices(stc_lda& L, const double* gate) {
   Ctx& c = *L.ctx;
   hipStream_t s = c.stream;
-  if (!L.cstream) HIP_CHECK(hipStreamCreateWithFlags(&L.cstream, hipStreamNonBlocking));
-  hipStream_t cs = L.cstream;
-  if (had_samp) HIP_CHECK(hipStreamWaitEvent(cs, L.ev_samp, 0));  // the next draw's count (side stream)
-  for (int j = 0; j < lay.nsub; ++j) {
-    if (!L.ev_rs[j]) HIP_CHECK(hipEventCreateWithFlags(&L.ev_rs[j], hipEventDisableTiming));
-    HIP_CHECK(hipStreamWaitEvent(cs, L.ev_ss[j], 0));
-    const int64_t w = stat_sub_rows(lay, j).second;
-    T* chunk = L.stat.as<T>() + (int64_t)lay.n * j * lay.vsj * L.kp;
-    coll_group_start(c);
-    coll_reduce_scatter(c, chunk, chunk + (int64_t)c.rank * w * L.kp, (size_t)(w * L.kp), RcclType<T>::v, cs);
-    if (j == 0) {
-      coll_all_reduce(c, L.small.p, (size_t)(L.k + 1), ncclFloat64, cs);
-      if (L.pre_inflight) coll_all_reduce(c, L.dcnt.as<int64_t>() + 3, 1, ncclInt64, cs);
-    }
-    coll_group_end(c);
-    if (j == 0 && L.pre_inflight) {
-      HIP_CHECK(hipMemcpyAsync(L.hpre, L.dcnt.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, cs));
-      HIP_CHECK(hipEventRecord(L.ev_pre, cs));
-      L.pre_inflight = false;
-      L.pre_valid = true;
-    }
-    HIP_CHECK(hipEventRecord(L.ev_rs[j], cs));
-  }
-  L.iteration += 1;
-  const double rho = std::pow(L.cfg.tau0 + (double)L.iteration, -L.cfg.kappa);
-  const double batch_size = std::ceil(L.cfg.mini_batch_fraction * (double)L.corpus_total);
-  const double scale = (double)L.corpus_total / batch_size;
-  const double* gate = L.small.as<double>() + L.k;
-  for (int j = 0; j < lay.nsub; ++j) {
-    HIP_CHECK(hipStreamWaitEvent(s, L.ev_rs[j], 0));
-    if (j == 0) record(L, 4);  // the statistics of sub-chunk 0 and the logphat / count sums are in
-    mstep_sub<T>(L, lay, c.rank, j, rho, scale, gate);
-  }
   const size_t nbs = (size_t)(L.Vs / lda::kRowsPerBlock), cnt = (size_t)(L.Vs * L.kp);
   coll_group_start(c);
   coll_all_gather(c, L.colpart.as<double>() + (size_t)c.rank * nbs * L.k, L.colpart.p, nbs * L.k, ncclFloat64, s);
@@ -1001,14 +860,13 @@ void train_tail_split(stc_lda& L, const lda::StatMap& lay, bool had_samp, int64_
   lda::launch_colsum_reduce(s, L.colpart.as<double>(), L.shards * (int64_t)nbs, L.k, gate, L.colsum.as<double>(),
                             L.psic.as<double>());
   L.lam_stale = true;
-  if (L.cfg.optimize_doc_concentration)
-    lda::launch_update_alpha(s, L.alpha.as<double>(), L.small.as<double>(), L.k, rho);
-  train_finish<T>(L, n, E, st);
 }
 
-template <typename T>
-void train_finish(stc_lda& L, int64_t n, int64_t E, stc_step_stats* st) {
+// updateAlpha, the step's timing and counters, and the caller's statistics
+void train_finish(stc_lda& L, const StepRates& sr, int64_t n, int64_t E, stc_step_stats* st) {
   hipStream_t s = L.ctx->stream;
+  if (L.cfg.optimize_doc_concentration)
+    lda::launch_update_alpha(s, L.alpha.as<double>(), L.small.as<double>(), L.k, sr.rho);
   record(L, 5);
   if (L.timing) {
     L.ev_pending[L.ev_set] = true;
@@ -1030,8 +888,98 @@ void train_finish(stc_lda& L, int64_t n, int64_t E, stc_step_stats* st) {
     st->inner_iters_max = (int32_t)h4[1];
     st->cap_hits = (int32_t)h4[2];
     st->nonempty_docs = (int64_t)ne;
-    st->rho = std::pow(L.cfg.tau0 + (double)L.iteration, -L.cfg.kappa);
+    st->rho = sr.rho;
   }
+}
+
+// train_tail's N-rank form with rs_chunks > 1 (stat_layout: nsub sub-chunks): sstats ran once per sub-chunk
+// (estep_and_stats split) and recorded ev_ss[j]; the reduce-scatter of sub-chunk j (one contiguous buffer in
+// that layout) runs on cstream as soon as ev_ss[j] fires — under the sstats launches of j+1… — with the
+// logphat / count all-reduce in sub-chunk 0's group, and the main stream runs the M-step of sub-chunk j under
+// the reduce-scatter of j+1.  Each element is summed over the same ranks in the same way as by the single
+// reduce-scatter, and sstats builds every row exactly as the single launch does, so the result is the
+// unchunked step's.
+template <typename T>
+void train_tail_split(stc_lda& L, const lda::StatMap& lay, bool had_samp, int64_t n, int64_t E,
+                      stc_step_stats* st) {
+  Ctx& c = *L.ctx;
+  hipStream_t s = c.stream, cs = L.cstream.get();
+  if (had_samp) HIP_CHECK(hipStreamWaitEvent(cs, L.ev_samp.e, 0));  // the next draw's count (side stream)
+  for (int j = 0; j < lay.nsub; ++j) {
+    HIP_CHECK(hipStreamWaitEvent(cs, L.ev_ss[j].e, 0));
+    const int64_t w = stat_sub_rows(lay, j).second;
+    T* chunk = L.stat.as<T>() + (int64_t)lay.n * j * lay.vsj * L.kp;
+    coll_group_start(c);
+    coll_reduce_scatter(c, chunk, chunk + (int64_t)c.rank * w * L.kp, (size_t)(w * L.kp), RcclType<T>::v, cs);
+    if (j == 0) {
+      coll_all_reduce(c, L.small.p, (size_t)(L.k + 1), ncclFloat64, cs);
+      if (L.pre_inflight) coll_all_reduce(c, L.dcnt.as<int64_t>() + 3, 1, ncclInt64, cs);
+    }
+    coll_group_end(c);
+    if (j == 0 && L.pre_inflight) publish_draw(L, cs);
+    HIP_CHECK(hipEventRecord(L.ev_rs[j].get(), cs));
+  }
+  L.iteration += 1;
+  const StepRates sr = step_rates(L);
+  for (int j = 0; j < lay.nsub; ++j) {
+    HIP_CHECK(hipStreamWaitEvent(s, L.ev_rs[j].e, 0));
+    if (j == 0) record(L, 4);  // the statistics of sub-chunk 0 and the logphat / count sums are in
+    mstep_sub<T>(L, lay, c.rank, j, sr.rho, sr.scale, sr.gate);
+  }
+  gather_slices<T>(L, sr.gate);
+  train_finish(L, sr, n, E, st);
+}
+
+// [U] submitMiniBatch tail: the stats merge (treeReduce ≙ RCCL), updateLambda, updateAlpha.
+//  * one GPU: the fused λ update + expElogβ' pass over all rows, then colsum and ψ(colsum).
+//  * N ranks: reduce-scatter of stat (each rank receives the summed rows of its vocabulary slice) and
+//    the logphat / count all-reduce in one group; the slice's fused λ update + expElogβ' pass; ONE
+//    group of all-gathers — the per-block colsum partials (k doubles per 64 rows), expElogβ' and
+//    logscale — then colsum reduced in the one-GPU block order, so it is identical on every rank.
+//    λ stays sharded (lam_stale) until a reader gathers it.  Per rank: stat (N−1)/N·V·kp·T bytes
+//    out, expElogβ' the same in, against 2(N−1)/N for an all-reduce, and 1/N of the M-step work.
+template <typename T>
+void train_tail(stc_lda& L, int64_t n, int64_t E, stc_step_stats* st) {
+  Ctx& c = *L.ctx;
+  hipStream_t s = c.stream;
+  const bool ranks = sharded(L);
+  const lda::StatMap lay = stat_layout(L);
+  if (L.tail_fault > 0 && --L.tail_fault == 0) {
+    throw Error(STC_ERR_STATE, "injected member failure between sstats and the reduce-scatter (STC_GROUP_STEP_FAULT)");
+  }
+  const bool had_samp = L.samp_pending;
+  if (L.samp_pending) {  // the next draw's counts (side stream) feed this step's collective / readback
+    HIP_CHECK(hipStreamWaitEvent(s, L.ev_samp.e, 0));
+    L.samp_pending = false;
+  }
+  if (ranks && lay.nsub > 1) {
+    train_tail_split<T>(L, lay, had_samp, n, E, st);
+    return;
+  }
+  if (c.coll()) {
+    coll_group_start(c);
+    if (ranks) {
+      const size_t cnt = (size_t)(L.Vs * L.kp);
+      coll_reduce_scatter(c, L.stat.p, L.stat.as<T>() + (size_t)c.rank * cnt, cnt, RcclType<T>::v, s);
+    }
+    coll_all_reduce(c, L.small.p, (size_t)(L.k + 1), ncclFloat64, s);
+    if (L.pre_inflight)  // the next draw's global batch size (word 3), for the next call
+      coll_all_reduce(c, L.dcnt.as<int64_t>() + 3, 1, ncclInt64, s);
+    coll_group_end(c);
+  }
+  if (L.pre_inflight) publish_draw(L, s);
+  record(L, 4);
+  L.iteration += 1;
+  const StepRates sr = step_rates(L);
+  if (ranks) {
+    mstep_slice<T>(L, c.rank, sr.rho, sr.scale, sr.gate);
+    gather_slices<T>(L, sr.gate);
+  } else {  // one GPU: all slices here (one unless STC_VIRTUAL_SHARDS)
+    for (int r = 0; r < L.shards; ++r) mstep_slice<T>(L, r, sr.rho, sr.scale, sr.gate);
+    lda::launch_colsum_reduce(s, L.colpart.as<double>(), L.shards * (L.Vs / lda::kRowsPerBlock), L.k, sr.gate,
+                              L.colsum.as<double>(), L.psic.as<double>());
+  }
+  train_finish(L, sr, n, E, st);
 }
 
 void require_ready(stc_lda& L) {
@@ -1113,9 +1061,6 @@ void next_impl(stc_lda& L, stc_step_stats* st) {
   L.s_cincl.reserve(4 * D);
   L.s_wincl.reserve(8 * D);
   L.s_sincl.reserve(4 * D);
-  if (!L.hcnt) HIP_CHECK(hipHostMalloc((void**)&L.hcnt, 4 * sizeof(int64_t), hipHostMallocDefault));
-  if (!L.hpre) HIP_CHECK(hipHostMalloc((void**)&L.hpre, 4 * sizeof(int64_t), hipHostMallocDefault));
-  if (!L.ev_pre) HIP_CHECK(hipEventCreateWithFlags(&L.ev_pre, hipEventDisableTiming));
   L.dcnt.reserve(4 * sizeof(int64_t));
   const int64_t draw = ++L.draws;
   claim_event_set(L);
@@ -1124,16 +1069,16 @@ void next_impl(stc_lda& L, stc_step_stats* st) {
   // the prefetched draw's batch is built on the side stream (behind its sampling, and behind the previous
   // step's E-step — ev_est), under the previous step's M-step and all-gathers
   const bool prefetched = L.pre_valid && L.pre_draw == draw;
-  const bool on_side = prefetched && L.prep_side && L.side && L.ev_est;
+  const bool on_side = prefetched && L.prep_side && L.side.s && L.ev_est.e;
   if (prefetched) {
-    wait_event(*L.ctx, L.ev_pre);
-    std::copy(L.hpre, L.hpre + 4, cnt);
+    wait_event(*L.ctx, L.ev_pre.e);
+    std::copy(L.hpre.p, L.hpre.p + 4, cnt);
   } else {
     sample_draw(L, draw, s, &L.scan_tmp);
     if (c.coll()) coll_all_reduce(c, L.dcnt.as<int64_t>() + 3, 1, ncclInt64, s);
-    HIP_CHECK(hipMemcpyAsync(L.hcnt, L.dcnt.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(L.hcnt.get(), L.dcnt.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
     wait_stream(*L.ctx, s);
-    std::copy(L.hcnt, L.hcnt + 4, cnt);
+    std::copy(L.hcnt.p, L.hcnt.p + 4, cnt);
   }
   L.pre_valid = false;
   const int64_t n = cnt[0], E = cnt[1], ns32 = cnt[2], n_global = cnt[3];
@@ -1144,8 +1089,8 @@ void next_impl(stc_lda& L, stc_step_stats* st) {
     return;
   }
   ensure_batch<T>(L, n, E, true);
-  const hipStream_t ps = on_side ? L.side : s;
-  if (on_side) HIP_CHECK(hipStreamWaitEvent(ps, L.ev_est, 0));
+  const hipStream_t ps = on_side ? L.side.s : s;
+  if (on_side) HIP_CHECK(hipStreamWaitEvent(ps, L.ev_est.e, 0));
   if (n > 0)
     lda::launch_fill_batch(ps, L.corpus->indptr.as<int64_t>(), D, L.wave_cap, L.s_counts.as<int32_t>(),
                            L.s_cincl.as<int32_t>(), L.s_sincl.as<int32_t>(), ns32, L.batch.as<int32_t>(),
@@ -1154,17 +1099,12 @@ void next_impl(stc_lda& L, stc_step_stats* st) {
   slot_offsets(L, n, ps, on_side ? &L.side_scan_tmp : &L.scan_tmp);
   const T* g0 = gen_gamma0<T>(L, ps, n, L.cfg.seed, L.iteration + 1, 0, 0);
   // the next draw, on the side stream beside this step's E-step, counted with this step's collective
-  if (!L.side) {
-    HIP_CHECK(hipStreamCreateWithFlags(&L.side, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&L.ev_fill, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&L.ev_samp, hipEventDisableTiming));
-    HIP_CHECK(hipEventCreateWithFlags(&L.ev_est, hipEventDisableTiming));
-  }
-  HIP_CHECK(hipEventRecord(L.ev_fill, ps));  // this draw's counts consumed and its batch built
-  if (on_side) HIP_CHECK(hipStreamWaitEvent(s, L.ev_fill, 0));
-  else HIP_CHECK(hipStreamWaitEvent(L.side, L.ev_fill, 0));
-  sample_draw(L, draw + 1, L.side, &L.side_scan_tmp);
-  HIP_CHECK(hipEventRecord(L.ev_samp, L.side));
+  const hipStream_t side = L.side.get();  // (the first next() makes it)
+  L.ev_est.get();  // from here on estep_and_stats records it
+  HIP_CHECK(hipEventRecord(L.ev_fill.get(), ps));  // this draw's counts consumed and its batch built
+  HIP_CHECK(hipStreamWaitEvent(on_side ? s : side, L.ev_fill.e, 0));
+  sample_draw(L, draw + 1, side, &L.side_scan_tmp);
+  HIP_CHECK(hipEventRecord(L.ev_samp.get(), side));
   L.samp_pending = true;
   L.pre_draw = draw + 1;
   if (c.coll()) {
@@ -1174,14 +1114,22 @@ void next_impl(stc_lda& L, stc_step_stats* st) {
     // (during this step's E-step), so the next call enqueues its batch preparation at once and the side stream
     // builds it under this step's sstats and M-step; read back in train_tail, after the E-step and sstats, the
     // preparation only started under the M-step and the next E-step waited for it (the "sample" phase, 0.29 ms)
-    HIP_CHECK(hipMemcpyAsync(L.hpre, L.dcnt.p, 4 * sizeof(int64_t), hipMemcpyDeviceToHost, L.side));
-    HIP_CHECK(hipEventRecord(L.ev_pre, L.side));
-    L.pre_inflight = false;
-    L.pre_valid = true;
+    publish_draw(L, side);
   }
   estep_and_stats<T>(L, n, ns32, E, g0, L.iteration + 1, true);
   train_tail<T>(L, n, E, st);
   L.prep_side = true;
+}
+
+// γ of the n slots' members (the launch's dtype) to the host, widened to double
+template <typename T>
+void read_gamma(stc_lda& L, int64_t n, double* gamma_out) {
+  if (!gamma_out || n <= 0) return;
+  hipStream_t s = L.ctx->stream;
+  std::vector<T> g((size_t)(n * L.k));
+  HIP_CHECK(hipMemcpyAsync(g.data(), L.gamma.p, sizeof(T) * g.size(), hipMemcpyDeviceToHost, s));
+  wait_stream(*L.ctx, s);
+  for (size_t j = 0; j < g.size(); ++j) gamma_out[j] = (double)g[j];
 }
 
 template <typename T>
@@ -1199,12 +1147,7 @@ void estep_only(stc_lda& L, const int64_t* ids, int64_t n, const double* gamma0,
   L.timing = false;
   estep_and_stats<T>(L, n, p.n_short, p.E, g0, L.iteration + 1, false, mixed_gamma0(L, gamma0, n), gamma_out != nullptr);
   L.timing = t;
-  if (gamma_out && n > 0) {
-    std::vector<T> g((size_t)(n * L.k));
-    HIP_CHECK(hipMemcpyAsync(g.data(), L.gamma.p, sizeof(T) * g.size(), hipMemcpyDeviceToHost, s));
-    wait_stream(*L.ctx, s);
-    for (size_t j = 0; j < g.size(); ++j) gamma_out[j] = (double)g[j];
-  }
+  read_gamma<T>(L, n, gamma_out);
   if (iters_out && n > 0) {
     HIP_CHECK(hipMemcpyAsync(iters_out, L.iters.p, 4 * n, hipMemcpyDeviceToHost, s));
   }
@@ -1247,12 +1190,7 @@ void infer_impl(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const
   a.iters = L.iters.as<int32_t>();
   a.bound = bound ? L.bound.as<double>() : nullptr;
   launch_split<T>(L, docs, a, n, p.n_short, false, bound, n > 0 ? (double)docs.nnz / (double)n : 0.0);
-  if (gamma_out && n > 0) {
-    std::vector<T> g((size_t)(n * L.k));
-    HIP_CHECK(hipMemcpyAsync(g.data(), L.gamma.p, sizeof(T) * g.size(), hipMemcpyDeviceToHost, s));
-    wait_stream(*L.ctx, s);
-    for (size_t j = 0; j < g.size(); ++j) gamma_out[j] = (double)g[j];
-  }
+  read_gamma<T>(L, n, gamma_out);
   if (bound) {
     double h[3] = {0, 0, 0};
     HIP_CHECK(hipMemsetAsync(L.scal.p, 0, sizeof(double) * 3, s));
@@ -1356,15 +1294,13 @@ int stc_lda_create(stc_ctx* ctx, const stc_lda_config* cfg, stc_lda** out) {
     if (L->mixed) {  // the fp64 workgroup kernel's shape at the fp32 row pitch, and the fp64 fast-kernel capacity
       L->P64 = ((L->kp / 2) % 2 == 1) ? L->kp : L->kp + 2;
       L->lds_rows64 = lda::estep_lds_rows<double>(L->k, L->kp, L->P64);
-      const int c64 = use_wide(L->k, STC_F64) ? lda::wide_row_cap(L->k) : lda::rows64_row_cap(L->k);
+      const int c64 = fast_row_cap(L->k, STC_F64);
       L->cap64 = c64 > 0 ? c64 : -1;
     }
-    const char* nw = std::getenv("STC_DISABLE_WAVE");
     // docs with nnz <= wave_cap run the register-resident kernel (fp32: lda_grid.hip, fp64:
     // lda_rows64.hip), the rest the workgroup kernel (lda.hip); −1: no slot is "short" (not even empty)
-    const int cap = use_wide(L->k, L->dtype) ? lda::wide_row_cap(L->k)
-                    : L->dtype == STC_F32 ? lda::grid_row_cap(L->k) : lda::rows64_row_cap(L->k);
-    L->wave_cap = (!(nw && nw[0] == '1') && cap > 0) ? cap : -1;
+    const int cap = fast_row_cap(L->k, L->dtype);
+    L->wave_cap = (!env_flag("STC_DISABLE_WAVE", false) && cap > 0) ? cap : -1;
     // α / η resolution ([U] OnlineLDAOptimizer.initialize)
     std::vector<double> alpha((size_t)L->k);
     const int alen = cfg->doc_concentration ? cfg->doc_concentration_len : 0;
@@ -1388,23 +1324,15 @@ int stc_lda_create(stc_ctx* ctx, const stc_lda_config* cfg, stc_lda** out) {
     L->cfg.doc_concentration = nullptr;
     L->cfg.doc_concentration_len = 0;
     L->nblocks_m = ceil_div(L->V, lda::kRowsPerBlock);
-    const char* vs = std::getenv("STC_VIRTUAL_SHARDS");
-    L->virt = vs ? std::max(1, std::min(64, std::atoi(vs))) : 1;
-    const char* ho = std::getenv("STC_HOT_ORDER");
-    L->hot_order = !(ho && ho[0] == '0');
-    const char* sd = std::getenv("STC_SORT_DOCS");
-    L->sort_docs = !(sd && sd[0] == '0');
-    const char* psr = std::getenv("STC_PRESORT");
-    L->presort = psr ? std::max(0, std::min(2, std::atoi(psr))) : 1;
-    const char* wt = std::getenv("STC_WIDE_TEAM");
-    L->team_force = wt ? std::max(0, std::min(8, std::atoi(wt))) : 0;
-    const char* tg = std::getenv("STC_TGRID");
-    L->tgrid = !(tg && tg[0] == '0');
-    L->tgrid_require = tg && tg[0] == '2';
-    const char* fc = std::getenv("STC_COLLECTIVE_MSTEP");
-    L->force_coll = fc && fc[0] == '1';
-    const char* rc = std::getenv("STC_RS_CHUNKS");
-    L->rs_chunks = rc ? std::max(1, std::min(16, std::atoi(rc))) : 4;
+    L->virt = env_int("STC_VIRTUAL_SHARDS", 1, 1, 64);
+    L->hot_order = env_flag("STC_HOT_ORDER", true);
+    L->sort_docs = env_flag("STC_SORT_DOCS", true);
+    L->presort = env_int("STC_PRESORT", 1, 0, 1) != 0;
+    L->team_force = env_int("STC_WIDE_TEAM", 0, 0, 8);
+    L->tgrid = env_flag("STC_TGRID", true);
+    L->tgrid_require = env_first("STC_TGRID") == '2';
+    L->force_coll = env_flag("STC_COLLECTIVE_MSTEP", false);
+    L->rs_chunks = env_int("STC_RS_CHUNKS", 4, 1, 16);
     ensure_layout(*L);  // λ, Bp, stat, logscale, colpart for the current shard count
     L->colsum.reserve(8 * L->k);
     L->psic.reserve(16 * L->k);  // ψ(colsum), exp(−ψ(colsum))
@@ -1416,7 +1344,7 @@ int stc_lda_create(stc_ctx* ctx, const stc_lda_config* cfg, stc_lda** out) {
     HIP_CHECK(hipMemcpyAsync(L->alpha.p, alpha.data(), 8 * L->k, hipMemcpyHostToDevice, ctx->stream));
     wait_stream(*ctx, ctx->stream);
     for (auto& s : L->ev)
-      for (auto& e : s) HIP_CHECK(hipEventCreate(&e));
+      for (auto& e : s) HIP_CHECK(hipEventCreate(&e.e));
     *out = L.release();
   });
 }
@@ -1428,7 +1356,7 @@ int stc_lda_destroy(stc_lda* lda) {
     // queued work first (with a communicator: a bounded wait; a collective that never completes is
     // aborted with its communicator, which releases its kernels, so the destroy returns)
     Ctx& c = *lda->ctx;
-    for (hipStream_t q : {c.stream, lda->side, lda->cstream}) {
+    for (hipStream_t q : {c.stream, lda->side.s, lda->cstream.s}) {
       if (!q) continue;
       try {
         wait_stream(c, q);
@@ -1456,7 +1384,6 @@ int stc_lda_set_corpus(stc_lda* L, const stc_dcsr* corpus, int64_t corpus_size_t
       L->vals32.reserve(4 * std::max<int64_t>(corpus->nnz, 1));
       lda::launch_to_f32(L->ctx->stream, corpus->values.as<double>(), L->vals32.as<float>(), corpus->nnz);
       wait_stream(*L->ctx, L->ctx->stream);
-      L->vals32_for = corpus;
     }
     L->corpus = corpus;
     L->corpus_total = corpus_size_total;

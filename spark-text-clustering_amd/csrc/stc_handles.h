@@ -2,6 +2,8 @@
 // that more than one of them fills in, and the host-side helpers of their entry points
 #pragma once
 
+#include <algorithm>
+#include <cstdlib>
 #include <initializer_list>
 #include <memory>
 #include <utility>
@@ -49,6 +51,65 @@ void with_temp(DevBuf& tmp, F&& f, bool run = true) {
   tmp.reserve(bytes);
   if (run) HIP_CHECK(f(tmp.p, bytes));
 }
+
+// Owners of the HIP objects a handle keeps: get() makes the object on first use, the destructor releases it;
+// the member itself is null until then (a handle asks "is there a side stream yet" that way).
+struct NoCopy {
+  NoCopy() = default;
+  NoCopy(const NoCopy&) = delete;
+  NoCopy& operator=(const NoCopy&) = delete;
+};
+struct Event : NoCopy {
+  hipEvent_t e = nullptr;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  hipEvent_t get(unsigned flags = hipEventDisableTiming) {
+    if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, flags));
+    return e;
+  }
+};
+struct Stream : NoCopy {
+  hipStream_t s = nullptr;
+  ~Stream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  hipStream_t get(unsigned flags = hipStreamNonBlocking, bool lowest_priority = false) {
+    if (!s && lowest_priority) {
+      int least = 0, greatest = 0;
+      HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+      HIP_CHECK(hipStreamCreateWithPriority(&s, flags, least));
+    }
+    if (!s) HIP_CHECK(hipStreamCreateWithFlags(&s, flags));
+    return s;
+  }
+};
+template <typename T, size_t N = 1>
+struct Pinned : NoCopy {  // N host words the device copies into; zero when made
+  T* p = nullptr;
+  ~Pinned() {
+    if (p) (void)hipHostFree(p);
+  }
+  T* get() {
+    if (!p) {
+      HIP_CHECK(hipHostMalloc((void**)&p, N * sizeof(T), hipHostMallocDefault));
+      std::fill(p, p + N, T{});
+    }
+    return p;
+  }
+};
+
+// Environment switches.  env_int: an integer clamped to [lo, hi], dflt when unset.  env_flag: by the value's
+// first character — a switch that is on by default is off only at '0', one that is off by default is on only at '1'.
+inline int env_int(const char* name, int dflt, int lo, int hi) {
+  const char* e = std::getenv(name);
+  return e ? std::max(lo, std::min(hi, std::atoi(e))) : dflt;
+}
+inline char env_first(const char* name) {  // the value's first character, 0 when unset or empty
+  const char* e = std::getenv(name);
+  return e ? e[0] : '\0';
+}
+inline bool env_flag(const char* name, bool dflt) { return dflt ? env_first(name) != '0' : env_first(name) == '1'; }
 
 // api.hip: off[0 .. n] of the host array `name` starts at 0, is non-decreasing and ends at `total` (spans) or
 // at most there; a host CSR's arrays (both return the largest gap: the longest document or row); and bufs'

@@ -609,3 +609,30 @@ def test_presorted_sstats_pairs_bitwise(ctx, monkeypatch, k):
     assert i0 == i1 == 5
     np.testing.assert_array_equal(l1, l0)
     np.testing.assert_array_equal(a1, a0)
+
+
+@pytest.mark.parametrize("k", [20, 100])
+def test_presorted_sstats_pairs_bitwise_own_stream(ctx, monkeypatch, k):
+    """The same comparison on handles that never call next(): they have no side stream, so the presort runs
+    on the handle's own lowest-priority sort stream.  Three step(ids, γ₀) and one estep(ids, γ₀) with
+    STC_PRESORT=1 give λ, α, γ, stat and the iteration counts of STC_PRESORT=0 bit for bit, every launch on
+    the rows kernels."""
+    rng = np.random.default_rng(47 + k)
+    corpus = random_corpus(rng, 400, 4096, 0, 250, empty_every=19)
+    ids = rng.permutation(400)[:301]
+    g0 = rng.gamma(100.0, 0.01, size=(ids.size, k))
+    runs = []
+    for presort in ("0", "1"):
+        monkeypatch.setenv("STC_PRESORT", presort)
+        h, _ = _handle(ctx, corpus, k, "f64", None, mini_batch_fraction=0.3, seed=9)
+        h.init_random(4)
+        for _ in range(3):
+            h.step(ids, g0, stats=False)
+        gamma, stat, iters = h.estep(ids, g0, want_stat=True)
+        kernels = h.counters()["kernels"]
+        assert kernels["k_estep_rows64"] >= 4 and kernels["k_estep"] == 0, kernels
+        runs.append((h.topics(), h.alpha(), gamma, stat, iters, h.iteration()))
+        h.close()
+    assert runs[0][-1] == runs[1][-1] == 3
+    for a, b in zip(runs[0], runs[1]):
+        np.testing.assert_array_equal(b, a)

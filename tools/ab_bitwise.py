@@ -1,10 +1,14 @@
 """A/B parity of two builds of libstc: the same E-step + a few next() steps, outputs compared bit for bit.
 
-    python tools/ab_bitwise.py LIB_A LIB_B [--docs N] [--k K] [--dtype f64] [--env-a VAR=VAL] [--env-b VAR=VAL]
+    python tools/ab_bitwise.py LIB_A LIB_B [--docs N] [--k K] [--vocab V] [--dtype f64|f32|mixed]
+                               [--env-a VAR=VAL] [--env-b VAR=VAL]
 
 Each library runs in its own child process (STC_LIB selects it); the child writes γ, stat, the iteration
-counts and λ after three next() steps to an .npz, and the parent compares the arrays with array_equal.
-Used to show a kernel variant (a build-time switch) leaves every output unchanged before timing it.
+counts, λ and α after three next() steps, and the launches per kernel family (counters()["kernels"], so a
+changed dispatch shows up), to an .npz, and the parent compares the arrays with array_equal.
+--dtype goes to LdaHandle as it is, so "mixed" runs the mixed-precision handle on the fp64 corpus.
+Used to show a kernel variant (a build-time switch) or a host-side change leaves every output unchanged
+before timing it.
 """
 import argparse
 import os
@@ -17,13 +21,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(out, docs, k, dtype):
+def child(out, docs, k, dtype, V):
     sys.path.insert(0, os.path.join(ROOT, "spark-text-clustering_amd"))
     import stc
     from stc import synth
 
     ctx = stc.Context.get(0)
-    V = 1 << 18
     corpus = synth.zipf_corpus(docs, 200, V, seed=7)
     # a few longer rows: R = 6 (the LDS row set) and the 7-8-set launch
     rng = np.random.default_rng(3)
@@ -36,7 +39,9 @@ def child(out, docs, k, dtype):
     gamma, stat, iters = h.estep(np.arange(docs), g0, want_stat=True)
     for _ in range(3):
         h.next(stats=False)
-    np.savez(out, gamma=gamma, stat=stat, iters=iters, lam=h.topics(), alpha=h.alpha())
+    kernels = h.counters()["kernels"]
+    np.savez(out, gamma=gamma, stat=stat, iters=iters, lam=h.topics(), alpha=h.alpha(),
+             kernels=np.array(list(kernels.values()), np.int64))
 
 
 def main():
@@ -44,13 +49,14 @@ def main():
     p.add_argument("libs", nargs=2)
     p.add_argument("--docs", type=int, default=20000)
     p.add_argument("--k", type=int, default=100)
+    p.add_argument("--vocab", type=int, default=1 << 18)
     p.add_argument("--dtype", default="f64")
     p.add_argument("--child", default=None)
     p.add_argument("--env-a", action="append", default=[], help="VAR=VAL set for the first run only")
     p.add_argument("--env-b", action="append", default=[], help="VAR=VAL set for the second run only")
     a = p.parse_args()
     if a.child:
-        child(a.child, a.docs, a.k, a.dtype)
+        child(a.child, a.docs, a.k, a.dtype, a.vocab)
         return
     outs = []
     with tempfile.TemporaryDirectory() as td:
@@ -58,8 +64,8 @@ def main():
             out = os.path.join(td, f"{i}.npz")
             env = dict(os.environ, STC_LIB=os.path.abspath(lib))
             env.update(kv.split("=", 1) for kv in (a.env_a if i == 0 else a.env_b))
-            subprocess.run([sys.executable, __file__, *a.libs, "--docs", str(a.docs), "--k", str(a.k), "--dtype",
-                            a.dtype, "--child", out], env=env, check=True)
+            subprocess.run([sys.executable, __file__, *a.libs, "--docs", str(a.docs), "--k", str(a.k), "--vocab",
+                            str(a.vocab), "--dtype", a.dtype, "--child", out], env=env, check=True)
             outs.append(dict(np.load(out)))
     ok = True
     for key in outs[0]:
@@ -67,7 +73,7 @@ def main():
         ok &= same
         print(f"{key}: {'bitwise equal' if same else 'DIFFERENT'}"
               + ("" if same else f" (max abs diff {np.max(np.abs(outs[0][key] - outs[1][key])):.3e})"))
-    print(f"mean iters {outs[0]['iters'].mean():.2f}")
+    print(f"mean iters {outs[0]['iters'].mean():.2f}, kernels {outs[0]['kernels'].tolist()}")
     sys.exit(0 if ok else 1)
 
 

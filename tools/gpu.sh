@@ -15,6 +15,7 @@
 #   prof               rocprofv3 stats + PMC passes of WORKLOADS="name:bench args;…" (each into
 #                      gpurun_out/prof_<name>; summarise with tools/pmc_summary.py --steady)
 #   bitwise            tools/ab_bitwise.py: each LIBS variant's E-step / next() outputs vs the in-tree library's
+#                      (BW_ARGS: further arguments, e.g. "--dtype f32")
 #   counters           one --pmc pass of $COUNTERS (those this rocprofv3 lists) over the headline E-step, of the
 #                      in-tree library and of each LIBS variant
 #   ubench             tools/ubench_f64 (the fp64 chain micro-benchmark)
@@ -68,7 +69,7 @@ r_configs() {
   done
 }
 r_bitwise() {
-  for n in $LIBS; do step bw_$n 400 python tools/ab_bitwise.py spark-text-clustering_amd/stc/libstc.so $(lib $n); done
+  for n in $LIBS; do step bw_$n 400 python tools/ab_bitwise.py spark-text-clustering_amd/stc/libstc.so $(lib $n) ${BW_ARGS:-}; done
 }
 r_cab() {  # r_cab CONFIG
   local B="python bench.py --config $1 --steps ${STEPS:-6} --warmup ${WARMUP:-2} $FAST"
