@@ -482,6 +482,42 @@ def topic_distribution(ids, cts, topics_matrix, alpha, gamma0, exp_elog_beta=Non
     return gamma / np.abs(gamma).sum()
 
 
+def doc_bound(ids, cts, elog_beta, alpha, gamma):
+    """One document's four terms of [U] LocalLDAModel.logLikelihoodBound from a given γ:
+    Σ_w cnt_w·logSumExp(E[log θ] + E[log β_w]) + Σ(α − γ)·E[log θ] + Σ(lgamma γ − lgamma α)
+    + lgamma Σα − lgamma Σγ.  elog_beta is V×k.  Entries with cts == 0 are skipped (their term is 0·x).
+    The token terms are added in entry order, as upstream's foreachActive adds them."""
+    ids = np.asarray(ids)
+    cts = np.asarray(cts, np.float64)
+    alpha = np.asarray(alpha, np.float64)
+    gamma = np.asarray(gamma, np.float64)
+    elog_theta = dirichlet_expectation(gamma)
+    nz = cts != 0
+    b = 0.0
+    if nz.any():
+        x = elog_beta[ids[nz]] + elog_theta                  # nnz × k
+        a = x.max(axis=1)
+        lse = a + np.log(np.exp(x - a[:, None]).sum(axis=1))
+        for t in (cts[nz] * lse).tolist():
+            b += t
+    b += np.sum((alpha - gamma) * elog_theta)
+    b += np.sum(gammaln(gamma) - gammaln(alpha))
+    b += gammaln(alpha.sum()) - gammaln(gamma.sum())
+    return b
+
+
+def topics_bound(topics_matrix, eta, elog_beta=None):
+    """[U] logLikelihoodBound's topicsPart E[log p(β|η) − log q(β|λ)]: Σ(η−λ)·Elogβ + Σ(lgamma λ − lgamma η)
+    + Σ_k (lgamma(Vη) − lgamma Σ_v λ_vk)   (upstream: `sum(lgamma(sumEta) - lgamma(sum(lambda(::,
+    breeze.linalg.*))))`, λ = topicsMatrix V×k).  elog_beta: dirichlet_expectation(λᵀ)ᵀ if the caller has it."""
+    lam = np.asarray(topics_matrix, np.float64)
+    if elog_beta is None:
+        elog_beta = dirichlet_expectation(lam.T).T
+    sum_eta = eta * lam.shape[0]
+    return (np.sum((eta - lam) * elog_beta) + np.sum(gammaln(lam) - gammaln(eta))
+            + np.sum(gammaln(sum_eta) - gammaln(lam.sum(axis=0))))
+
+
 def log_likelihood_bound(docs, gamma0s, topics_matrix, alpha, eta):
     """[U] LocalLDAModel.logLikelihoodBound: corpusPart + topicsPart (ELBO).
 
@@ -497,19 +533,8 @@ def log_likelihood_bound(docs, gamma0s, topics_matrix, alpha, eta):
         if len(ids) == 0 or not np.any(np.asarray(cts) != 0):
             continue
         gamma, _, _ = variational_topic_inference(ids, cts, eeb, alpha, g0)
-        elog_theta = dirichlet_expectation(gamma)
-        b = 0.0
-        for i, c in zip(ids, cts):
-            b += c * log_sum_exp(elog_theta + elog_beta[i])
-        b += np.sum((alpha - gamma) * elog_theta)
-        b += np.sum(gammaln(gamma) - gammaln(alpha))
-        b += gammaln(alpha.sum()) - gammaln(gamma.sum())
-        corpus += b
-    # E[log p(β|η) − log q(β|λ)]: Σ(η−λ)·Elogβ + Σ(lgamma λ − lgamma η) + Σ_k (lgamma(Vη) − lgamma Σ_v λ_vk)
-    # (upstream: `sum(lgamma(sumEta) - lgamma(sum(lambda(::, breeze.linalg.*))))`, λ = topicsMatrix V×k)
-    sum_eta = eta * V
-    topics = (np.sum((eta - lam) * elog_beta) + np.sum(gammaln(lam) - gammaln(eta))
-              + np.sum(gammaln(sum_eta) - gammaln(lam.sum(axis=0))))
+        corpus += doc_bound(ids, cts, elog_beta, alpha, gamma)
+    topics = topics_bound(lam, eta, elog_beta)
     return corpus + topics, corpus, topics
 
 

@@ -43,6 +43,12 @@ template <typename T>
 __device__ __forceinline__ T eps_floor() { return T(1.17549435e-38); }  // FLT_MIN (f32 only)
 template <>
 __device__ __forceinline__ double eps_floor<double>() { return 0.0; }
+// BOUND: a dot product below this may have lost products to underflow (each below FLT_MIN / DBL_MIN, so all k of
+// them are a negligible part of a dot at the floor); such a row's token term is evaluated in log space
+template <typename T>
+__device__ __forceinline__ T lse_floor() { return T(1e-25); }
+template <>
+__device__ __forceinline__ double lse_floor<double>() { return 1e-280; }
 
 template <typename T, typename VT>
 __device__ __forceinline__ T hsum(VT v);
@@ -235,7 +241,8 @@ __device__ __forceinline__ void estep_doc(const EStepArgs<T>& a, unsigned char* 
       const T phi = dot + fmax(exp_t(lse - lmax), eps_floor<T>());
       const T cn = cts[n];
       rr[n] = cn / phi;
-      if (BOUND && (done || it >= a.max_iter) && cn != T(0)) {  // logSumExp: no epsilon
+      // logSumExp: no epsilon (with λ at hand the token terms are taken after the loop instead, see there)
+      if (BOUND && !a.lam && (done || it >= a.max_iter) && cn != T(0)) {
         b_tok += (double)cn * ((double)log(fmax(dot, eps_floor<T>())) + a.logscale[ids[n]]);
         c_tok += (double)cn;
       }
@@ -309,11 +316,53 @@ __device__ __forceinline__ void estep_doc(const EStepArgs<T>& a, unsigned char* 
       topic += (al - g) * el + (lgamma(g) - lgamma(al));
       asum += al;
     }
+    // With λ at hand (a.lam) the token terms are formed here, from the last pass's dot products computed once
+    // more, so that one comparison decides a row's form: log(dot) + m_v as above, or — a dot under lse_floor has
+    // lost products to underflow — [U] logLikelihoodBound's own cnt · logSumExp_t(E[log θ_t] + E[log β_vt]) with
+    // E[log β_vt] = ψ(λ_vt) − ψ(Σ_v λ_vt).  The block takes a round's marked rows one at a time.  Block-uniform.
+    double lse_tok = 0.0;
+    if (a.lam) {
+      for (int base = 0; base < nnz; base += kBlock) {
+        const int n = base + tid;
+        T mark = T(0);
+        if (n < nnz && cts[n] != T(0)) {
+          const T* Brow = LDS ? s_B + n * P : a.Bp + (int64_t)ids[n] * kp;
+          VT acc = (VT)T(0);
+          for (int c = 0; c < ncg; ++c)
+            acc += *reinterpret_cast<const VT*>(Brow + c * W) * *reinterpret_cast<const VT*>(s_eth + c * W);
+          const T dot = hsum<T, VT>(acc);
+          if (dot < lse_floor<T>()) {
+            mark = cts[n];
+          } else {
+            b_tok += (double)cts[n] * ((double)log(dot) + a.logscale[ids[n]]);
+            c_tok += (double)cts[n];
+          }
+        }
+        if (!__syncthreads_or(mark != T(0))) continue;
+        s_part[tid] = mark;  // (free since the last Phase C)
+        __syncthreads();
+        for (int i = 0; i < kBlock && base + i < nnz; ++i) {
+          const T cn = s_part[i];
+          if (cn == T(0)) continue;
+          const double* lrow = a.lam + (int64_t)ids[base + i] * k;
+          double mx = -INFINITY, z0 = 0.0, z1 = 0.0;
+          for (int t = tid; t < k; t += kBlock)
+            mx = fmax(mx, (digamma_t<double>(lrow[t]) - a.psic[t]) + (digamma_t<double>((double)s_gam[t]) - psisum));
+          block_reduce3(z0, z1, mx, s_red);
+          double se = 0.0, dm = -INFINITY;
+          for (int t = tid; t < k; t += kBlock)
+            se += exp((digamma_t<double>(lrow[t]) - a.psic[t]) + (digamma_t<double>((double)s_gam[t]) - psisum) - mx);
+          block_reduce3(se, z1, dm, s_red);
+          lse_tok += (double)cn * (mx + log(se));
+        }
+        __syncthreads();  // s_part is rewritten by the next round
+      }
+    }
     double tok = b_tok + c_tok * elog_max;
     block_reduce3(tok, topic, dummy2, s_red);
     double as2 = asum, z = 0.0, dz = -INFINITY;
     block_reduce3(as2, z, dz, s_red);
-    if (tid == 0) a.bound[mem] = tok + topic + (lgamma(as2) - lgamma(gsum));
+    if (tid == 0) a.bound[mem] = (tok + lse_tok) + topic + (lgamma(as2) - lgamma(gsum));
   }
 }
 

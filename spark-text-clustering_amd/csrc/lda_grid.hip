@@ -454,10 +454,23 @@ __device__ __forceinline__ void grid_doc(const EStepArgs<float>& a, GLds<S>& sm,
   }
   if (BOUND) {
     // token terms from the group-0 lanes of wave 0 (each row once); topic terms summed over waves
+    // Σγ in fp64, of the very γ_t the topic terms take: for a document of little mass (Σ cnt ≪ 1: TF·IDF
+    // values) those terms cancel to ≈ ψ(Σγ)·(Σγ − Σ_t γ_t), which the fp32 sum of the exchange above leaves at
+    // ≈ 1e-7·Σγ — 1e-4 of such a document's bound
+    const double al = d.own ? a.alpha[t] : 0.0;
+    const double gd = d.own ? (double)d.gam : 0.0;
+    double gsd = wave_sum(gd);
+    if constexpr (W > 1) {
+      if (lane == 0) sm.bd[wave][0] = gsd;
+      __syncthreads();
+      gsd = 0.0;
+      for (int w = 0; w < W; ++w) gsd += sm.bd[w][0];
+      __syncthreads();  // bd is rewritten below
+    }
+    const double psisum_b = digamma_t<double>(gsd);  // (the outputs above keep the fp32 sum's)
     double topic = 0.0, as = 0.0;
     if (d.own) {
-      const double gd = (double)d.gam, al = a.alpha[t];
-      const double el = digamma_t<double>(gd) - psisum;
+      const double el = digamma_t<double>(gd) - psisum_b;
       topic = (al - gd) * el + (lgamma(gd) - lgamma(al));
       as = al;
     }
@@ -475,8 +488,8 @@ __device__ __forceinline__ void grid_doc(const EStepArgs<float>& a, GLds<S>& sm,
         tp += sm.bd[w][0];
         asw += sm.bd[w][1];
       }
-      const double elog_max = (double)d.cs - psisum;  // log of the scale eθ carried (≈ 0)
-      a.bound[mem] = tok + ct * elog_max + tp + (lgamma(asw) - lgamma((double)gsum));
+      const double elog_max = (double)d.cs - psisum_b;  // log of the scale eθ carried (≈ 0)
+      a.bound[mem] = tok + ct * elog_max + tp + (lgamma(asw) - lgamma(gsd));
     }
   }
 }

@@ -73,6 +73,9 @@ struct EStepArgs {
   // slots + one count word), filled on the device before the long-document launch walks it (last, so
   // the other kernels' argument layout is unchanged)
   int32_t* long_list = nullptr;
+  // BOUND: λ (V×k) for the log-space token term of a row whose scaled dot product underflowed (lda_wide.hip, lda.hip);
+  // nullptr (λ sharded, only this rank's slice current): such a row keeps the floored logarithm
+  const double* lam = nullptr;
 };
 
 // the largest double x with fl(x / k) ≤ 1e-3 (host; see EStepArgs::stop_thr)

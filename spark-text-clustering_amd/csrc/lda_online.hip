@@ -1189,6 +1189,7 @@ void infer_impl(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const
   a.gamma = gamma_out ? L.gamma.as<T>() : nullptr;
   a.iters = L.iters.as<int32_t>();
   a.bound = bound ? L.bound.as<double>() : nullptr;
+  a.lam = bound && !L.lam_stale ? L.lam.as<double>() : nullptr;
   launch_split<T>(L, docs, a, n, p.n_short, false, bound, n > 0 ? (double)docs.nnz / (double)n : 0.0);
   read_gamma<T>(L, n, gamma_out);
   if (bound) {

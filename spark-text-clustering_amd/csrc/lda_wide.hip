@@ -42,6 +42,9 @@ struct WTr<float> {
   static __device__ __forceinline__ float psi(float x) { return digamma_fast(x); }
   static __device__ __forceinline__ float eps_floor() { return kTiny; }
   static __device__ __forceinline__ float eps_cap() { return 3.0e38f; }
+  // BOUND: below this a dot product may have lost terms to underflow (each lost B'·eθ' product is < FLT_MIN, so
+  // k ≤ 2048 of them are < 2.5e-35: under 3e-10 of a dot ≥ 1e-25; a healthy dot is ≳ exp(−ψ(Σ_v λ_vt))/k)
+  static __device__ __forceinline__ float lse_floor() { return 1e-25f; }
   // 16 values → this lane's row of the chunk, summed over the wave (see the header)
   static __device__ __forceinline__ float rs16(const float* x, int lane) {
     float a[8], b[4], c[2];
@@ -82,6 +85,8 @@ struct WTr<double> {
   static __device__ __forceinline__ double psi(double x) { return digamma_fast_d(x); }
   static __device__ __forceinline__ double eps_floor() { return 0.0; }
   static __device__ __forceinline__ double eps_cap() { return 1e300; }
+  // (as the fp32 one: lost products are < DBL_MIN each, under 1e-24 of a dot ≥ 1e-280)
+  static __device__ __forceinline__ double lse_floor() { return 1e-280; }
   static __device__ __forceinline__ double rs16(const double* x, int lane) {
     double a[8], b[4], c[2];
     swap_add_nd<true, 8>(x, x + 8, a);
@@ -406,9 +411,17 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
         const T r = cts[j] * Tr::rcp(dot + eps[j]);
         sm.rr[n] = r;
         rd = fma(r, dot, rd);
-        if (BOUND && last && cts[j] != T(0)) {
-          b_tok += (double)cts[j] * (log(fmax((double)dot, 1e-300)) + a.logscale[sm.ids[n]]);
-          c_tok += (double)cts[j];
+        if (BOUND && last) {
+          // a dot product below lse_floor has lost terms to underflow (B' or eθ' entries, or their products):
+          // the row is marked (xs[0][n], read by this thread alone until barrier (2)) and its term is
+          // evaluated in log space after the loop
+          const bool under = cts[j] != T(0) && a.lam && dot < Tr::lse_floor();
+          sm.xs[0][n] = under ? T(1) : T(0);
+          sm.xs[1][n] = cts[j];
+          if (cts[j] != T(0) && !under) {
+            b_tok += (double)cts[j] * (log(fmax((double)dot, 1e-300)) + a.logscale[sm.ids[n]]);
+            c_tok += (double)cts[j];
+          }
         }
       }
     }
@@ -515,17 +528,45 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
       sm.bd[wave][3] = ct;
     }
     __syncthreads();
-    if (tid == 0) {
-      double tp = 0.0, aw = 0.0, tk = 0.0, cw = 0.0;
-      for (int w = 0; w < kWWaves; ++w) {
-        tp += sm.bd[w][0];
-        aw += sm.bd[w][1];
-        tk += sm.bd[w][2];
-        cw += sm.bd[w][3];
-      }
-      // token terms used the loop's ψ(Σγ') (cs) in eθ; move them to the exact ψ(Σγ)
-      a.bound[mem] = tk + cw * ((double)cs - psisum) + tp + (lgamma(aw) - lgamma(gsum));
+    double tp = 0.0, aw = 0.0, tk = 0.0, cw = 0.0;
+    for (int w = 0; w < kWWaves; ++w) {
+      tp += sm.bd[w][0];
+      aw += sm.bd[w][1];
+      tk += sm.bd[w][2];
+      cw += sm.bd[w][3];
     }
+    // the marked rows ([U] logLikelihoodBound's own form): cnt · logSumExp_t(E[log θ_t] + E[log β_vt]) with
+    // E[log β_vt] = ψ(λ_vt) − ψ(Σ_v λ_vt), each lane on its Q topics.  Block-uniform; once per such row.
+    double lse_tok = 0.0;
+    for (int n = 0; n < nnz; ++n) {
+      if (sm.xs[0][n] == T(0)) continue;
+      __syncthreads();  // bd: the sums above, or the previous marked row
+      const int64_t v = sm.ids[n];
+      double x[Q], mx = -INFINITY;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const int t = t0 + q;
+        x[q] = t < k ? (digamma_t<double>(a.lam[v * k + t]) - a.psic[t]) + (digamma_t<double>((double)gam[q]) - psisum)
+                     : -INFINITY;
+        mx = fmax(mx, x[q]);
+      }
+      mx = wave_max(mx);
+      if (lane == 0) sm.bd[wave][0] = mx;
+      __syncthreads();
+      mx = sm.bd[0][0];
+      for (int w = 1; w < kWWaves; ++w) mx = fmax(mx, sm.bd[w][0]);
+      double se = 0.0;
+#pragma unroll
+      for (int q = 0; q < Q; ++q) se += exp(x[q] - mx);  // exp(−∞) = 0 past k
+      se = wave_sum(se);
+      if (lane == 0) sm.bd[wave][1] = se;
+      __syncthreads();
+      se = sm.bd[0][1];
+      for (int w = 1; w < kWWaves; ++w) se += sm.bd[w][1];
+      lse_tok += (double)sm.xs[1][n] * (mx + log(se));
+    }
+    // token terms used the loop's ψ(Σγ') (cs) in eθ; move them to the exact ψ(Σγ)
+    if (tid == 0) a.bound[mem] = (tk + cw * ((double)cs - psisum)) + lse_tok + tp + (lgamma(aw) - lgamma(gsum));
   }
 }
 

@@ -75,6 +75,23 @@ def planted_corpus(rng, D, V, k, L=60, alpha=0.1):
     return stc.CsrMatrix.from_rows(rows, V), topics
 
 
+def oracle_iterates(O, ids, cts, eeb, elog_beta, alpha, gamma0, width):
+    """The oracle's stopping iteration `it` of one document and {j: (γ_j, b_j)} for max(1, it − width) ≤ j ≤
+    it + width: γ_j = variational_topic_inference(..., n_iter=j)[0], b_j = doc_bound(γ_j).  The fixed
+    point's whole state is γ (eθ and φnorm are recomputed from it by the same operations), so γ_{j+1} is
+    one n_iter=1 run from γ_j, bit for bit the n_iter=j+1 run from γ₀ — the window costs one extra pass."""
+    g_it, _, it = O.variational_topic_inference(ids, cts, eeb, alpha, gamma0)
+    lo = max(1, it - width)
+    g = O.variational_topic_inference(ids, cts, eeb, alpha, gamma0, n_iter=lo)[0]
+    out = {}
+    for j in range(lo, it + width + 1):
+        if j > lo:
+            g = O.variational_topic_inference(ids, cts, eeb, alpha, g, n_iter=1)[0]
+        out[j] = (g, float(O.doc_bound(ids, cts, elog_beta, alpha, g)))
+    assert np.array_equal(out[it][0], g_it)
+    return it, out
+
+
 def random_tokens(rng, n_docs, max_len=30, vocab=None):
     """Token lists covering every UTF-8 tail length 0–3 and multi-byte characters."""
     alphabet = list("abcdefghijklmnopqrstuvwxyz") + ["é", "ß", "ж", "中", "🙂", "Ω", "ü"]
