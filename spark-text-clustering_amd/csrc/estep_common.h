@@ -1,6 +1,6 @@
 // estep_common.h — pieces shared by the register-resident E-step kernels (lda_grid.hip,
-// lda_grid.hip): Spark's φ epsilon in log space, packed-FMA operand type, reduce-scatter helpers
-// and the diagnostic s_memtime stamps.
+// lda_rows64.hip, lda_wide.hip, lda_team64.hip): Spark's φ epsilon in log space, packed-FMA operand
+// type, reduce-scatter helpers and the diagnostic s_memtime stamps.
 #pragma once
 
 #include "lda_kernels.h"

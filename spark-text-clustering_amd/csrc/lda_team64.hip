@@ -96,32 +96,6 @@ struct TTeam {
   unsigned spin_limit;
 };
 
-// the P partials of granule slot `idx` summed in member order (this member contributes `mine`); a lane
-// with need = false reads nothing.  A wave whose partners never publish gives up (bounded spin): it sets
-// the timeout word and s_abort, and its sums are garbage (the caller leaves at the next barrier).
-__device__ __forceinline__ double team_sum(const TTeam& t, unsigned epoch, int idx, double mine, bool need, int* s_abort) {
-  const int base = (int)(epoch & 1) * t.P * t.xstride;
-  double sum = 0.0;
-  for (int m = 0; m < t.P; ++m) {
-    double v = 0.0;
-    if (m == t.member) {
-      v = mine;
-    } else {
-      for (unsigned spins = 0;; ++spins) {
-        const bool ok = !need || get_granule<double>(t.rs, base + m * t.xstride + idx, epoch, v);
-        if (__builtin_amdgcn_ballot_w64(!ok) == 0) break;
-        if (spin_give_up(spins, t.tmo, t.spin_limit)) {
-          *s_abort = 1;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-    sum += need ? v : 0.0;
-  }
-  return sum;
-}
-
 // worker lanes, γ₀ / α / ψc of the member's topics, Σγ₀ / Σα over all k topics, Σcts, the first eθ;
 // false (outputs written) for a document without a nonzero count
 template <int KL, bool STATS>
@@ -506,7 +480,7 @@ __device__ __forceinline__ bool tg_close(const EStepArgs<double>& a, TLds<KL>& s
       const int base = (int)(epoch & 1) * t.P * t.xstride + t.member * t.xstride;
       put_granule<double>(t.rs, base + kTSlotG, epoch, gp);
     }
-    const double gsum = team_sum(t, epoch, kTSlotG, gp, true, s_abort);
+    const double gsum = team_sum<double>(t.rs, t.P, t.member, t.xstride, t.tmo, t.spin_limit, epoch, kTSlotG, gp, true, s_abort);
     if (lane == 0) sm.ac[3] = digamma_t<double>(gsum);
   }
   __syncthreads();
@@ -617,19 +591,11 @@ bool launch_estep_tgrid64(hipStream_t s, const EStepArgs<double>& a, bool stats,
   if (a.n == 0) return true;
   if (wt.P != tgrid64_members(a.kp) || wt.xstride < kTXStride)
     throw Error(STC_ERR_INVALID_ARG, "fp64 team-grid E-step: members / granule stride do not match k");
-  auto go = [&](const void* kern) {
-    int dev = 0, cus = 0, per_cu = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kTThreads, 0));
-    if ((int64_t)per_cu * cus < wt.blocks) return false;
-    EStepArgs<double> aa = a;
-    WideTeam ww = wt;
-    void* args[] = {&aa, &ww};
-    HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)wt.blocks), dim3(kTThreads), args, 0, s));
-    return true;
-  };
-  return stats ? go((const void*)k_estep_tgrid64<kTKL, true>) : go((const void*)k_estep_tgrid64<kTKL, false>);
+  const void* kern = stats ? (const void*)k_estep_tgrid64<kTKL, true> : (const void*)k_estep_tgrid64<kTKL, false>;
+  EStepArgs<double> aa = a;
+  WideTeam ww = wt;
+  void* args[] = {&aa, &ww};
+  return launch_resident(kern, wt.blocks, kTThreads, 0, args, s);
 }
 
 }  // namespace lda

@@ -74,12 +74,10 @@ struct WTr<double> {
   static __device__ __forceinline__ double wsum(double v) { return wave_sum_d(v); }
   static __device__ __forceinline__ double rcp(double x) { return rcp_nr(x); }
   // eθ' = exp(ψ(g) − cs − ψc): pc holds ψc
+  // stc_internal.h's ψ + libm exp; psi64.h's chain (exp_digamma_minus_v2<2>, as k_estep_rows64) measured
+  // neutral at config 4 (277 ms either way over 20 steps after 10 warm-up)
   static __device__ __forceinline__ double eth(double g, double cs, double pc) {
-#if WIDE_PSI_V2
-    return exp_digamma_minus_v2<2>(g, cs + pc);  // psi64.h: branch-free, constants as SGPR operands
-#else
     return exp_digamma_minus_d(g, cs + pc);
-#endif
   }
   static __device__ __forceinline__ double pcload(const double* psic, int k, int t) { (void)k; return psic[t]; }
   static __device__ __forceinline__ double psi(double x) { return digamma_fast_d(x); }
@@ -217,24 +215,18 @@ __host__ __device__ constexpr size_t wide_lds_fixed() {
   return (sizeof(WLds<T>) + 255) / 256 * 256;
 }
 
-#ifndef WIDE_PSI_V2
-// fp64 γ update through psi64.h's chain (as k_estep_rows64) instead of exp_digamma_minus_d + libm exp:
-// one ψ/exp form across the fp64 E-step kernels; measured neutral at config 4 (277 ms either way over
-// 20 steps after 10 warm-up), parity unchanged
-#define WIDE_PSI_V2 1
-#endif
-#ifndef WIDE_LB_BYTES
-#define WIDE_LB_BYTES 64  // streamed-row loads in flight per lane (bytes)
-#endif
-#ifndef WIDE_NR64_Q1
-#define WIDE_NR64_Q1 64
-#endif
-#ifndef WIDE_NR64_Q2
-#define WIDE_NR64_Q2 24
-#endif
-#ifndef WIDE_NR64_Q4
-#define WIDE_NR64_Q4 8
-#endif
+constexpr int WIDE_LB_BYTES = 64;  // streamed-row loads in flight per lane (bytes)
+// fp64 register rows per topics-per-lane Q (wide_nr below)
+constexpr int WIDE_NR64_Q1 = 64;
+constexpr int WIDE_NR64_Q2 = 24;
+constexpr int WIDE_NR64_Q4 = 8;
+// streamed rows whose loads are in flight together (at most a Phase A chunk)
+template <typename T, int Q>
+constexpr int wide_lb() {
+  constexpr int lb = (int)(WIDE_LB_BYTES / (sizeof(T) * Q));
+  return lb < wide_chunk<T, Q>() ? lb : wide_chunk<T, Q>();
+}
+
 template <typename T, int Q, int NR, bool STATS, bool BOUND>
 __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -243,7 +235,7 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
   using Tr = WTr<T>;
   constexpr int CH = wide_chunk<T, Q>();
   static_assert(NR % 8 == 0 && NR % CH == 0, "Phase A takes register rows CH, Phase B 8 at a time");
-  constexpr int LB = (int)(WIDE_LB_BYTES / (sizeof(T) * Q)) < CH ? (int)(WIDE_LB_BYTES / (sizeof(T) * Q)) : CH;
+  constexpr int LB = wide_lb<T, Q>();
   if ((int64_t)blockIdx.x >= a.n) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t slot = a.slot0 + blockIdx.x;
@@ -319,7 +311,9 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
     }
     return;
   }
-  // Σγ₀, Σα, Σcts over the block (one LDS round)
+  // Σγ₀, Σα, Σcts over the block (one LDS round).  Nothing reads Σcts, and it stays: without these ≈ 30
+  // instructions the kernel does the same work in the same instructions and config 4 fp64 runs 3.4 % slower
+  // on it (554.2 against 535.8 ms per E-step)
   {
     T ct = T(0);
 #pragma unroll
@@ -600,7 +594,7 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_mc(EStepArgs<T> a, int
   using Tr = WTr<T>;
   constexpr int CH = wide_chunk<T, Q>();
   static_assert(NR % 8 == 0 && NR % CH == 0, "Phase A takes register rows CH, Phase B 8 at a time");
-  constexpr int LB = (int)(WIDE_LB_BYTES / (sizeof(T) * Q)) < CH ? (int)(WIDE_LB_BYTES / (sizeof(T) * Q)) : CH;
+  constexpr int LB = wide_lb<T, Q>();
   const int P = wt.P;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = (int)blockIdx.x, il = b / 8;
@@ -822,19 +816,6 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_mc(EStepArgs<T> a, int
         }
         const int g0 = base + m * (int)wt.xstride;
         T v[Q], vs = T(0);
-#ifdef STC_TEAM_NOWAIT  // timing-only diagnostic build: read whatever is there (wrong results)
-        if (true) {
-          get_granule<T>(rs, g0 + kp, epoch, vs);
-#pragma unroll
-          for (int q = 0; q < Q; ++q) {
-            v[q] = T(0);
-            if (t0 + q < kp) get_granule<T>(rs, g0 + t0 + q, epoch, v[q]);
-          }
-          vs = T(0);
-#pragma unroll
-          for (int q = 0; q < Q; ++q) v[q] = T(0);
-        } else
-#endif
         for (unsigned spins = 0;; ++spins) {
           // the Σ r·dot granule is the same for every lane: lane 0 polls it, the wave takes it by readlane
           bool ok = lane != 0 || get_granule<T>(rs, g0 + kp, epoch, vs);
@@ -952,7 +933,7 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_tc(EStepArgs<T> a, int
   using Tr = WTr<T>;
   constexpr int CH = wide_chunk<T, Q>();
   static_assert(NR % 8 == 0 && NR % CH == 0, "Phase A takes register rows CH, Phase B 8 at a time");
-  constexpr int LB = (int)(WIDE_LB_BYTES / (sizeof(T) * Q)) < CH ? (int)(WIDE_LB_BYTES / (sizeof(T) * Q)) : CH;
+  constexpr int LB = wide_lb<T, Q>();
   constexpr int GD = kWRows, GS = kWRows + 1;  // granule slots: row partials [0, nnz), Σ|Δγ|, Σγ
   const int P = wt.P;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -967,32 +948,6 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_tc(EStepArgs<T> a, int
   unsigned epoch = 0;
   if (tid == 0) s_abort = 0;
   STAMP_DECL
-
-  // one exchange: publish `mine` at slot `idx` (if `pub`), then the member-order sum of slot `idx`
-  // over the team (every lane of a wave takes part in the poll; `need` = this lane reads the slot)
-  auto exchange = [&](int idx, T mine, bool pub, bool need) -> T {
-    const int base = (int)(epoch & 1) * P * (int)wt.xstride;
-    if (pub && pub_ok) put_granule<T>(rs, base + member * (int)wt.xstride + idx, epoch, mine);
-    T sum = T(0);
-    for (int m = 0; m < P; ++m) {
-      T v = T(0);
-      if (m == member) {
-        v = mine;
-      } else {
-        for (unsigned spins = 0;; ++spins) {
-          const bool ok = !need || get_granule<T>(rs, base + m * (int)wt.xstride + idx, epoch, v);
-          if (__all(ok)) break;
-          if (spin_give_up(spins, wt.tmo, wt.spin_limit)) {
-            if (lane == 0) s_abort = 1;
-            break;
-          }
-          __builtin_amdgcn_s_sleep(1);
-        }
-      }
-      sum += v;
-    }
-    return sum;
-  };
 
   for (int64_t j = team; j < a.n; j += nteams) {
     const int64_t slot = a.slot0 + j;
@@ -1040,7 +995,7 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_tc(EStepArgs<T> a, int
           if (a.gamma) a.gamma[mem * k + t] = T(0);
           if (STATS) a.elogth[slot * k + t] = T(0);
         }
-        if (STATS && t < kp && q + Q * tid < kP) a.eth[slot * kp + t] = T(0);
+        if (STATS && t < kp) a.eth[slot * kp + t] = T(0);
       }
       if (member == 0) {
         if (tid < nnz) {
@@ -1255,7 +1210,10 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_tc(EStepArgs<T> a, int
     double gpart = 0.0;
     for (int w = 0; w < kWWaves; ++w) gpart += sm.bd[w][0];
     ++epoch;
-    const double gsum = (double)exchange(GS, (T)gpart, tid == 0, true);
+    if (pub_ok && tid == 0)
+      put_granule<T>(rs, (int)(epoch & 1) * P * (int)wt.xstride + member * (int)wt.xstride + GS, epoch, (T)gpart);
+    const double gsum =
+        (double)team_sum<T>(rs, P, member, (int)wt.xstride, wt.tmo, wt.spin_limit, epoch, GS, (T)gpart, true, &s_abort);
     if (s_abort) return;
     const double psisum = digamma_t<double>(gsum);
 #pragma unroll
@@ -1265,7 +1223,7 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_tc(EStepArgs<T> a, int
         if (a.gamma) a.gamma[mem * k + t] = gam[q];
         if (STATS) a.elogth[slot * k + t] = (T)(digamma_t<double>((double)gam[q]) - psisum);
       }
-      if (STATS && t < kp && q + Q * tid < kP) a.eth[slot * kp + t] = t < k ? eth[q] : T(0);
+      if (STATS && t < kp) a.eth[slot * kp + t] = t < k ? eth[q] : T(0);
     }
     if (member == 0 && tid == 0) {
       if (a.iters) a.iters[mem] = it;
@@ -1279,7 +1237,9 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide_tc(EStepArgs<T> a, int
 
 // register rows per (T, Q): NR·Q·sizeof(T)/4 ≈ 128 VGPRs, so 512 threads keep two waves per SIMD
 // (fp32 Q = 1 — config 4's k = 500 — takes 176 rows: 227 VGPRs, no spills, the most the register
-// file holds at two waves per SIMD; its streamed tail is what bounds that config)
+// file holds at two waves per SIMD; its streamed tail is what bounds that config).  The team kernels take
+// the same rows: their persistent loop holds more live state and they spill, but (measured) those spills
+// sit outside the inner loop, so nothing is cut
 template <typename T, int Q>
 constexpr int wide_nr() {
   return (sizeof(T) == 4 && Q == 1) ? 176
@@ -1288,32 +1248,38 @@ constexpr int wide_nr() {
                                     : (int)(128 * 4 / (sizeof(T) * Q)) / kWChunk * kWChunk;
 }
 
-// the team kernel's register rows: WIDE_MC_NR_CUT Phase-A chunks fewer than the one-CU kernel (its
-// persistent loop holds more live state; measured: the spills of the uncut form sit outside the inner
-// loop, so the default cuts nothing)
-#ifndef WIDE_MC_NR_CUT
-#define WIDE_MC_NR_CUT 0
-#endif
+// the LDS of a launch: `fixed` bytes of per-row arrays, then as many block rows (nl) as the CU's LDS holds;
+// static_word: 256 B left for the team kernels' own static word (s_abort)
+struct WidePlan {
+  int nl;
+  size_t lds;
+};
 template <typename T, int Q>
-constexpr int wide_nr_mc() {
-  return wide_nr<T, Q>() - WIDE_MC_NR_CUT * wide_chunk<T, Q>();
+WidePlan wide_lds_plan(size_t fixed, bool static_word) {
+  const size_t row_bytes = sizeof(T) * kWThreads * Q;
+  const int nl = (int)((kWLds - fixed - (static_word ? 256 : 0)) / row_bytes);
+  return {nl, fixed + (size_t)nl * row_bytes};
 }
 
-template <typename T, int Q>
-void launch_q(hipStream_t s, const EStepArgs<T>& a, bool stats, bool bound) {
-  constexpr int NR = wide_nr<T, Q>();
-  const size_t fixed = wide_lds_fixed<T>();
-  const size_t row_bytes = sizeof(T) * kWThreads * Q;
-  const int nl = (int)((kWLds - fixed) / row_bytes);
-  const size_t lds = fixed + (size_t)nl * row_bytes;
-  auto go = [&](auto kern) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    kern<<<dim3((unsigned)a.n), kWThreads, lds, s>>>(a, nl);
-    KERNEL_CHECK();
-  };
-  if (stats) go(k_estep_wide<T, Q, NR, true, false>);
-  else if (bound) go(k_estep_wide<T, Q, NR, false, true>);
-  else go(k_estep_wide<T, Q, NR, false, false>);
+// f(integral_constant<int, Q>) with the Q ∈ {1, 2, 4} topics per lane that cover q·512 topics
+template <typename F>
+auto wide_with_q(int q, const char* too_many, F&& f) {
+  if (q <= 1) return f(std::integral_constant<int, 1>{});
+  if (q <= 2) return f(std::integral_constant<int, 2>{});
+  if (q <= 4) return f(std::integral_constant<int, 4>{});
+  throw Error(STC_ERR_INVALID_ARG, too_many);
+}
+inline int wide_q_of(int k) { return (k + kWThreads - 1) / kWThreads; }
+
+// a team kernel on the persistent grid (false: not resident, nothing launched)
+template <typename T, typename K>
+bool launch_team(K kern, hipStream_t s, const EStepArgs<T>& a, const WidePlan& p, const WideTeam& wt) {
+  HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+  EStepArgs<T> aa = a;
+  int nl = p.nl;
+  WideTeam ww = wt;
+  void* args[] = {&aa, &nl, &ww};
+  return launch_resident((const void*)kern, wt.blocks, kWThreads, p.lds, args, s);
 }
 
 }  // namespace
@@ -1323,116 +1289,65 @@ int wide_row_cap(int k) { return k <= kWThreads * 4 ? kWRows : 0; }
 // rows one CU keeps resident (VGPRs + LDS) for this (T, k): the team size for a document of nnz rows
 template <typename T>
 int wide_resident_rows(int k) {
-  auto rows = [](auto q) {
+  // a planning figure, asked for any k: past 2048 topics it answers as for Q = 4 (the clamp; nothing is thrown)
+  return wide_with_q(std::min(wide_q_of(k), 4), "", [](auto q) {
     constexpr int Q = decltype(q)::value;
-    const size_t row_bytes = sizeof(T) * kWThreads * Q;
-    return wide_nr_mc<T, Q>() + (int)((kWLds - wide_lds_fixed<T>() - 256) / row_bytes);
-  };
-  if (k <= kWThreads) return rows(std::integral_constant<int, 1>{});
-  if (k <= 2 * kWThreads) return rows(std::integral_constant<int, 2>{});
-  return rows(std::integral_constant<int, 4>{});
+    return wide_nr<T, Q>() + wide_lds_plan<T, Q>(wide_lds_fixed<T>(), true).nl;
+  });
 }
-
-// The persistent team grid, launched only if every block can be resident at once: the kernel's
-// occupancy (blocks per CU at this LDS size) × the device's CUs must cover the grid (false: nothing
-// launched, the caller runs the one-CU kernel).  A plain launch, not hipLaunchCooperativeKernel: the
-// cooperative launch path made every profiled process (rocprofv3 --kernel-trace) fault at exit inside
-// the HSA runtime's teardown, after the profiler's finalisation (r03 exit probe: libamdhip64 exit
-// handler → libhsa-runtime64, on a /dev/dri mapping already released).  Residency is checked here; a
-// block that is nonetheless not co-resident (another process on the device) only delays its team, and
-// the bounded spins turn a delay past the limit into a timeout word, on which the host re-runs the
-// same slots on the one-CU kernel (api.hip launch_split).
-inline bool launch_resident(const void* kern, int blocks, size_t lds, void** args, hipStream_t s) {
-  int dev = 0, cus = 0, per_cu = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, kWThreads, lds));
-  if ((int64_t)per_cu * cus < blocks) return false;
-  HIP_CHECK(hipLaunchKernel(kern, dim3((unsigned)blocks), dim3(kWThreads), args, lds, s));
-  return true;
-}
-
-template <typename T, int Q>
-bool launch_q_mc(hipStream_t s, const EStepArgs<T>& a, bool stats, const WideTeam& wt) {
-  bool ok = true;
-  constexpr int NR = wide_nr_mc<T, Q>();
-  const size_t fixed = wide_lds_fixed<T>();
-  const size_t row_bytes = sizeof(T) * kWThreads * Q;
-  int nl = (int)((kWLds - fixed - 256) / row_bytes);  // 256 B for the kernel's own static word
-  const size_t lds = fixed + (size_t)nl * row_bytes;
-  auto go = [&](auto kern) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    EStepArgs<T> aa = a;
-    WideTeam ww = wt;
-    void* args[] = {&aa, &nl, &ww};
-    ok = launch_resident((const void*)kern, wt.blocks, lds, args, s);
-  };
-  if (stats) go(k_estep_wide_mc<T, Q, NR, true>);
-  else go(k_estep_wide_mc<T, Q, NR, false>);
-  return ok;
-}
-
-template <typename T, int Q>
-bool launch_q_tc(hipStream_t s, const EStepArgs<T>& a, bool stats, WideTeam wt) {
-  bool ok = true;
-  constexpr int NR = wide_nr_mc<T, Q>();
-  // the per-row arrays: the launch's longest document (every one when unknown), at least the register rows
-  const int mr = wt.max_row >= 0 && wt.max_row <= kWRows ? wt.max_row : kWRows;
-  wt.xrows = (std::max(mr, std::max(NR, 2)) + 1) / 2 * 2;
-  const size_t fixed = tc_lds_fixed<T>(wt.xrows);
-  const size_t row_bytes = sizeof(T) * kWThreads * Q;
-  int nl = (int)((kWLds - fixed - 256) / row_bytes);
-  const size_t lds = fixed + (size_t)nl * row_bytes;
-  auto go = [&](auto kern) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    EStepArgs<T> aa = a;
-    WideTeam ww = wt;
-    void* args[] = {&aa, &nl, &ww};
-    ok = launch_resident((const void*)kern, wt.blocks, lds, args, s);
-  };
-  if (stats) go(k_estep_wide_tc<T, Q, NR, true>);
-  else go(k_estep_wide_tc<T, Q, NR, false>);
-  return ok;
-}
-
-// topic split: member topics 512·Q with Q = ⌈k / (512·P)⌉ ≤ 4
-template <typename T>
-bool launch_estep_wide_tc(hipStream_t s, const EStepArgs<T>& a, bool stats, const WideTeam& wt) {
-  if (a.n == 0) return true;
-  const int q = (a.k + kWThreads * wt.P - 1) / (kWThreads * wt.P);
-  if (q <= 1) return launch_q_tc<T, 1>(s, a, stats, wt);
-  if (q <= 2) return launch_q_tc<T, 2>(s, a, stats, wt);
-  if (q <= 4) return launch_q_tc<T, 4>(s, a, stats, wt);
-  throw Error(STC_ERR_INVALID_ARG, "topic-split team E-step: k > 2048·P");
-}
-template bool launch_estep_wide_tc<float>(hipStream_t, const EStepArgs<float>&, bool, const WideTeam&);
-template bool launch_estep_wide_tc<double>(hipStream_t, const EStepArgs<double>&, bool, const WideTeam&);
-
-template <typename T>
-bool launch_estep_wide_mc(hipStream_t s, const EStepArgs<T>& a, bool stats, const WideTeam& wt) {
-  if (a.n == 0) return true;
-  if (a.k <= kWThreads) return launch_q_mc<T, 1>(s, a, stats, wt);
-  if (a.k <= 2 * kWThreads) return launch_q_mc<T, 2>(s, a, stats, wt);
-  if (a.k <= 4 * kWThreads) return launch_q_mc<T, 4>(s, a, stats, wt);
-  throw Error(STC_ERR_INVALID_ARG, "wide E-step: k > 2048");
-}
-
 template int wide_resident_rows<float>(int);
 template int wide_resident_rows<double>(int);
-template bool launch_estep_wide_mc<float>(hipStream_t, const EStepArgs<float>&, bool, const WideTeam&);
-template bool launch_estep_wide_mc<double>(hipStream_t, const EStepArgs<double>&, bool, const WideTeam&);
 
 template <typename T>
 void launch_estep_wide(hipStream_t s, const EStepArgs<T>& a, bool stats, bool bound) {
   if (a.n == 0) return;
-  if (a.k <= kWThreads) launch_q<T, 1>(s, a, stats, bound);
-  else if (a.k <= 2 * kWThreads) launch_q<T, 2>(s, a, stats, bound);
-  else if (a.k <= 4 * kWThreads) launch_q<T, 4>(s, a, stats, bound);
-  else throw Error(STC_ERR_INVALID_ARG, "wide E-step: k > 2048");
+  wide_with_q(wide_q_of(a.k), "wide E-step: k > 2048", [&](auto q) {
+    constexpr int Q = decltype(q)::value, NR = wide_nr<T, Q>();
+    const WidePlan p = wide_lds_plan<T, Q>(wide_lds_fixed<T>(), false);
+    auto go = [&](auto kern) {
+      HIP_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds));
+      kern<<<dim3((unsigned)a.n), kWThreads, p.lds, s>>>(a, p.nl);
+      KERNEL_CHECK();
+    };
+    if (stats) go(k_estep_wide<T, Q, NR, true, false>);
+    else if (bound) go(k_estep_wide<T, Q, NR, false, true>);
+    else go(k_estep_wide<T, Q, NR, false, false>);
+  });
 }
-
 template void launch_estep_wide<float>(hipStream_t, const EStepArgs<float>&, bool, bool);
 template void launch_estep_wide<double>(hipStream_t, const EStepArgs<double>&, bool, bool);
+
+template <typename T>
+bool launch_estep_wide_mc(hipStream_t s, const EStepArgs<T>& a, bool stats, const WideTeam& wt) {
+  if (a.n == 0) return true;
+  return wide_with_q(wide_q_of(a.k), "wide E-step: k > 2048", [&](auto q) {
+    constexpr int Q = decltype(q)::value, NR = wide_nr<T, Q>();
+    const WidePlan p = wide_lds_plan<T, Q>(wide_lds_fixed<T>(), true);
+    return stats ? launch_team<T>(k_estep_wide_mc<T, Q, NR, true>, s, a, p, wt)
+                 : launch_team<T>(k_estep_wide_mc<T, Q, NR, false>, s, a, p, wt);
+  });
+}
+template bool launch_estep_wide_mc<float>(hipStream_t, const EStepArgs<float>&, bool, const WideTeam&);
+template bool launch_estep_wide_mc<double>(hipStream_t, const EStepArgs<double>&, bool, const WideTeam&);
+
+// topic split: member topics 512·Q with Q = ⌈k / (512·P)⌉ ≤ 4
+template <typename T>
+bool launch_estep_wide_tc(hipStream_t s, const EStepArgs<T>& a, bool stats, const WideTeam& wt0) {
+  if (a.n == 0) return true;
+  const int qm = (a.k + kWThreads * wt0.P - 1) / (kWThreads * wt0.P);
+  return wide_with_q(qm, "topic-split team E-step: k > 2048·P", [&](auto q) {
+    constexpr int Q = decltype(q)::value, NR = wide_nr<T, Q>();
+    // the per-row arrays: the launch's longest document (every one when unknown), at least the register rows
+    WideTeam wt = wt0;
+    const int mr = wt.max_row >= 0 && wt.max_row <= kWRows ? wt.max_row : kWRows;
+    wt.xrows = (std::max(mr, std::max(NR, 2)) + 1) / 2 * 2;
+    const WidePlan p = wide_lds_plan<T, Q>(tc_lds_fixed<T>(wt.xrows), true);
+    return stats ? launch_team<T>(k_estep_wide_tc<T, Q, NR, true>, s, a, p, wt)
+                 : launch_team<T>(k_estep_wide_tc<T, Q, NR, false>, s, a, p, wt);
+  });
+}
+template bool launch_estep_wide_tc<float>(hipStream_t, const EStepArgs<float>&, bool, const WideTeam&);
+template bool launch_estep_wide_tc<double>(hipStream_t, const EStepArgs<double>&, bool, const WideTeam&);
 
 }  // namespace lda
 }  // namespace stc

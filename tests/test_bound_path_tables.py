@@ -72,8 +72,11 @@ def test_wide_rows():
     waves = threads // waves_of
     nr64 = {q: _const(src, f"WIDE_NR64_Q{q}") for q in (1, 2, 4)}
     assert "(sizeof(T) == 4 && Q == 1) ? 176" in src and "(int)(128 * 4 / (sizeof(T) * Q)) / kWChunk * kWChunk" in src
-    assert _const(src, "WIDE_MC_NR_CUT") == 0  # wide_resident_rows counts the team kernel's register rows
-    assert "return wide_nr_mc<T, Q>() + (int)((kWLds - wide_lds_fixed<T>() - 256) / row_bytes);" in src
+    # wide_resident_rows counts the team kernels' register rows, which are the one-CU kernel's (no cut), and the
+    # LDS rows planned with 256 B less
+    assert "wide_nr_mc" not in src and "WIDE_MC_NR_CUT" not in src
+    assert "return wide_nr<T, Q>() + wide_lds_plan<T, Q>(wide_lds_fixed<T>(), true).nl;" in src
+    assert "const int nl = (int)((kWLds - fixed - (static_word ? 256 : 0)) / row_bytes);" in src
     for (dtype, q), table in T.WIDE_ROWS.items():
         size = 8 if dtype == "f64" else 4
         fixed = (size * (waves * rows + rows + 2 * waves) + 4 * rows + 8 * waves * 4 + 255) // 256 * 256

@@ -9,7 +9,8 @@
 #   ab                 headline + planted lines of the in-tree library and of each LIBS variant
 #                      (libstc_<n>.so); DTYPE=f32 for the fp32 kernels; ROUNDS=n interleaves n rounds
 #   configs            BASELINE configs 4 / 5 lines, fp64 + fp32, with the CPU baseline (DTYPES narrows)
-#   c4ab / c5ab        config 4 / 5 A/B of the LIBS variants against the in-tree library (STEPS, WARMUP)
+#   c4ab / c5ab        config 4 / 5 A/B of the LIBS variants against the in-tree library (STEPS, WARMUP, DTYPE;
+#                      ROUNDS=n interleaves n rounds)
 #   c2env/c4env/c5env  config 2 / 4 / 5 lines of the in-tree library under each ENVS="name:VAR=val,…" setting
 #   feat               the featurisation line + its kernel profile + FETCH / WRITE passes
 #   prof               rocprofv3 stats + PMC passes of WORKLOADS="name:bench args;…" (each into
@@ -72,9 +73,13 @@ r_bitwise() {
   for n in $LIBS; do step bw_$n 400 python tools/ab_bitwise.py spark-text-clustering_amd/stc/libstc.so $(lib $n) ${BW_ARGS:-}; done
 }
 r_cab() {  # r_cab CONFIG
-  local B="python bench.py --config $1 --steps ${STEPS:-6} --warmup ${WARMUP:-2} $FAST"
-  for n in $LIBS; do step c$1_$n 500 env STC_LIB=$(lib $n) $B; done
-  step c$1_new 500 $B
+  local B="python bench.py --config $1 --steps ${STEPS:-6} --warmup ${WARMUP:-2} $FAST ${DTYPE:+--dtype $DTYPE}"
+  local r s
+  for r in $(seq 1 ${ROUNDS:-1}); do  # ROUNDS > 1: the builds interleaved, logs suffixed _r<round>
+    [ ${ROUNDS:-1} -gt 1 ] && s=_r$r || s=
+    for n in $LIBS; do step c$1_$n$s 500 env STC_LIB=$(lib $n) $B; done
+    step c$1_new$s 500 $B
+  done
 }
 r_cenv() {  # r_cenv CONFIG: the in-tree library under each ENVS="name:VAR=val[,VAR=val] …" setting
   local B="python bench.py --config $1 --steps ${STEPS:-6} --warmup ${WARMUP:-2} $FAST"
