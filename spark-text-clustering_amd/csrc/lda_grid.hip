@@ -562,7 +562,7 @@ size_t lds_pad() {
 template <class S, bool SKIPLONG>
 bool launch_g_persist(hipStream_t s, const EStepArgs<float>& a, bool stats, bool bound) {
   if (!GRID_PERSIST || !a.long_list || lds_pad() != 0 || bound) return false;  // (the bound kernels spill resident)
-  int32_t* ticket = a.long_list + a.n + 1;  // the word past the long-document list (api.hip reserves it)
+  int32_t* ticket = a.long_list + a.n + 1;  // the word past the long-document list (lda_online.hip launch_split reserves it)
   auto go = [&](const void* kern) {
     int dev = 0, cus = 0, per_cu = 0;
     HIP_CHECK(hipGetDevice(&dev));

@@ -17,6 +17,7 @@
 #include "collectives.h"
 #include "lda_kernels.h"
 #include "lda_online.h"
+#include "lda_step_kernels.h"
 #include "stc_handles.h"
 
 using namespace stc;
@@ -1195,7 +1196,7 @@ void infer_impl(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const
   if (bound) {
     double h[3] = {0, 0, 0};
     HIP_CHECK(hipMemsetAsync(L.scal.p, 0, sizeof(double) * 3, s));
-    if (n > 0) lda::launch_sum_f64(s, L.bound.as<double>(), n, L.scal.as<double>());
+    if (n > 0) lda::launch_sum_vals<double>(s, L.bound.as<double>(), n, L.scal.as<double>());
     if (docs.nnz > 0) lda::launch_sum_vals<T>(s, docs.values.as<T>(), docs.nnz, L.scal.as<double>() + 1);
     HIP_CHECK(hipMemcpyAsync(h, L.scal.p, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
     wait_stream(*L.ctx, s);
@@ -1220,9 +1221,9 @@ void topics_part(stc_lda& L, double* elem_part, double* norm_part) {
   }
   HIP_CHECK(hipMemsetAsync(L.dtmp.p, 0, sizeof(double) * nb, s));
   if (vn > 0)
-    lda::launch_topics_bound<T>(s, L.lam.as<double>() + v0 * L.k, L.colsum.as<double>(), vn, L.k, L.eta,
+    lda::launch_topics_bound(s, L.lam.as<double>() + v0 * L.k, L.colsum.as<double>(), vn, L.k, L.eta,
                                 L.dtmp.as<double>(), nb);
-  lda::launch_sum_f64(s, L.dtmp.as<double>(), nb, L.scal.as<double>() + 3);
+  lda::launch_sum_vals<double>(s, L.dtmp.as<double>(), nb, L.scal.as<double>() + 3);
   double part = 0.0;
   std::vector<double> cs((size_t)L.k);
   HIP_CHECK(hipMemcpyAsync(&part, L.scal.as<double>() + 3, sizeof(double), hipMemcpyDeviceToHost, s));

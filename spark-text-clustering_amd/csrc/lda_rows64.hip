@@ -638,7 +638,7 @@ __device__ __forceinline__ void rows64_close(const EStepArgs<double>& a, RLds<S>
     const int ws = (n >> 3) & 3, q = 8 * (n >> 5) + (n & 7);  // row n = 32·set + 8·wave + row lane
     const double rv = sm.rrow[ws][q];
     a.r[e0 + n] = rv;
-    if (STATS && a.keys) {  // (null: the pairs were built and sorted beside the E-step, api.hip presort)
+    if (STATS && a.keys) {  // (null: the pairs were built and sorted beside the E-step, lda_online.hip estep_and_stats)
       a.keys[e0 + n] = (uint32_t)sm.rid[ws][q];
       a.vals[e0 + n] = entry_val<double>(slot, e0 + n, rv);
     }
@@ -785,7 +785,7 @@ __global__ __launch_bounds__(64 * kW, R64_LONG_OCC) void k_estep_rows64_long(ESt
 template <class S, int NPSI>
 bool launch_persist(hipStream_t s, const EStepArgs<double>& a, bool stats, bool bound) {
   if (!a.long_list || bound) return false;  // (the bound E-step keeps a workgroup per slot)
-  int32_t* ticket = a.long_list + a.n + 1;  // the word past the long-document list (api.hip reserves it)
+  int32_t* ticket = a.long_list + a.n + 1;  // the word past the long-document list (lda_online.hip launch_split reserves it)
   auto go = [&](const void* kern) {
     int dev = 0, cus = 0, per_cu = 0;
     HIP_CHECK(hipGetDevice(&dev));

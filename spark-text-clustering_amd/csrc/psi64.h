@@ -14,7 +14,7 @@ namespace psi64 {
 // form with its coefficient as the instruction's SGPR operand (a GFX9 VOP3 takes one constant-bus
 // operand), so no constant costs a v_mov pair; branch-free (the shift part is computed for every lane
 // and selected), so the compiler cannot sink it into a divergent branch.  Same Breeze series and
-// truncation fix as stc_internal.h exp_digamma_minus_d; exp() is Cody–Waite + a degree-13 Taylor
+// truncation fix as estep_common.h exp_digamma_minus_d; exp() is Cody–Waite + a degree-13 Taylor
 // polynomial in even/odd halves (truncation 4e-18 relative).
 __device__ __forceinline__ double fma_s(double a, double b, double c) {  // a·b + c, c in an SGPR pair
   double d;

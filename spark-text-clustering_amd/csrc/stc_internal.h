@@ -149,7 +149,7 @@ struct Recycler {
 // ---------------------------------------------------------------------------------------
 // Context: one device, one stream, optional RCCL communicator.
 // ---------------------------------------------------------------------------------------
-struct LocalColl;  // in-process collectives of the stc_group members that share one device (api.hip)
+struct LocalColl;  // in-process collectives of the stc_group members that share one device (collectives.h)
 struct Ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -168,9 +168,9 @@ struct Ctx {
   int64_t tf_fallbacks = 0;     // single passes that fell back to the sorted-key passes
   bool idf_cache = true;  // idf.hip: the device IDF model's hot-idf LDS table (STC_IDF_NO_CACHE=1: off)
   Recycler recycle;    // freed stc_dcsr allocations for the next outputs (stc_dcsr_free)
-  DevBuf scratch[12];  // grow-only scratch of the featurisation kernels (hashing_tf.hip, idf.hip, api.hip IDF)
+  DevBuf scratch[12];  // grow-only scratch of the featurisation kernels (hashing_tf.hip, idf.hip, features_api.hip IDF)
   DevBuf coll_tmp;    // the in-process all-reduce's staging buffer
-  // RCCL failure handling (api.hip wait_stream / wait_event): with a communicator, every wait on work that
+  // RCCL failure handling (collectives.hip wait_stream / wait_event): with a communicator, every wait on work that
   // may hold a collective polls with a deadline instead of blocking in the runtime
   const std::atomic<bool>* abort_flag = nullptr;  // the group's: set once any of its members has failed
   std::atomic<bool> comm_aborted{false};          // comm was aborted (ncclCommAbort): never used again
@@ -237,261 +237,6 @@ __host__ __device__ inline double gamma_sample(uint64_t stream, int topic, doubl
 __host__ __device__ inline uint64_t train_doc_key(int64_t iteration, int rank, int64_t pos) {
   return (((uint64_t)iteration & 0xFFFFFFull) << 40) | (((uint64_t)rank & 0xFFull) << 32) |
          ((uint64_t)pos & 0xFFFFFFFFull);
-}
-
-// ---------------------------------------------------------------------------------------
-// Breeze 0.13.2 digamma / trigamma (recurrence to x > 5 + asymptotic series).
-// ---------------------------------------------------------------------------------------
-template <typename R>
-__host__ __device__ inline R digamma_t(R x) {
-  R r = 0;
-  while (x <= R(5)) {
-    r -= R(1) / x;
-    x += R(1);
-  }
-  const R f = R(1) / (x * x);
-  const R t = f * (R(-1.0 / 12.0) + f * (R(1.0 / 120.0) + f * (R(-1.0 / 252.0) + f * (R(1.0 / 240.0) +
-              f * (R(-1.0 / 132.0) + f * (R(691.0 / 32760.0) + f * (R(-1.0 / 12.0) + f * R(3617.0) / R(8160.0))))))));
-  return r + log(x) - R(0.5) / x + t;
-}
-// ln x for positive normal x: v_log_f32 (log2) · ln 2, without the denormal-range fixup __logf carries
-__device__ __forceinline__ float ln_pos(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994531f; }
-// fp32 digamma for the E-step inner loop: ψ(x) = ψ(x+4) − 1/x − (3x²+12x+11)/((x+1)(x+2)(x+3))
-// unconditionally (no data-dependent loop ⇒ no lane divergence; the three shifted reciprocals share
-// one v_rcp_f32, 1/x keeps its own for the small-γ end), v_log_f32, and Breeze's asymptotic series
-// at x+4 ≥ 4 (first omitted term < 2e-9).  Accuracy vs the shift-6 form: tools/dg_check.py.
-__device__ inline float digamma_fast(float x) {
-  const float num = fmaf(fmaf(3.f, x, 12.f), x, 11.f);
-  const float den = fmaf(fmaf(x + 6.f, x, 11.f), x, 6.f);
-  const float r = __builtin_amdgcn_rcpf(x) + num * __builtin_amdgcn_rcpf(den);
-  const float y = x + 4.f;
-  const float iy = __builtin_amdgcn_rcpf(y);
-  const float f = iy * iy;
-  const float t = f * (-1.f / 12.f + f * (1.f / 120.f + f * (-1.f / 252.f + f * (1.f / 240.f + f * (-1.f / 132.f)))));
-  return ln_pos(y) - 0.5f * iy + t - r;
-}
-
-// fp64 1/q from v_rcp_f64 and two Newton steps (≤ 1 ulp apart from the correctly rounded quotient)
-__device__ __forceinline__ double rcp_nr(double q) {
-  double r = __builtin_amdgcn_rcp(q);
-  r = fma(r, fma(-q, r, 1.0), r);
-  return fma(r, fma(-q, r, 1.0), r);
-}
-// Breeze evaluates its 8-term asymptotic series S8 at y_B = x + ⌊5 − x⌋ + 1 ∈ (5, 6]; the fast forms
-// below evaluate it at x + 6 ∈ (6, 11] (one rational for the six recurrence terms).  S8's truncation
-// error E(y) = ψ(y) − S8(y) reaches 8e-13 at y = 5, which a slowly-dying topic of a long E-step
-// amplifies past 1e-7 relative, so the difference E(x + 6) − E(y_B) is added back: E(y) = f⁹·P(f),
-// f = 1/y², P fitted to 7e-18 absolute on y ∈ [5, 11.5] (tools/fit_breeze_digamma.py).
-__device__ __forceinline__ double breeze_trunc(double iy) {
-  const double f = iy * iy, f2 = f * f, f4 = f2 * f2;
-  return f4 * f4 * f * (-3.053401198888146 + f * (26.284421368293753 + f * (-260.94994774566294 +
-                        f * (2372.137971404805 + f * -12318.55039822477))));
-}
-__device__ __forceinline__ double breeze_shift_fix(double x, double iy6, bool sh) {
-  const double yb = sh ? x + (floor(5.0 - x) + 1.0) : 6.0;  // E needs ~1e-4 relative: raw v_rcp_f64
-  return breeze_trunc(iy6) - breeze_trunc(__builtin_amdgcn_rcp(yb));
-}
-// fp64 digamma for the M-step's V×k elements, branch-free: Breeze's recurrence Σ_{i<6} 1/(x+i) for
-// x ≤ 5 as one rational Q'(x)/Q(x), Q = x(x+1)…(x+5), the same 8-term asymptotic series at y = x + 6
-// (or y = x when x > 5, where Breeze does not shift) and breeze_shift_fix.  Agrees with
-// digamma_t<double> to a few ulp; the loop form costs a divergent chain of up to six fp64 divisions.
-__device__ inline double digamma_fast_d(double x) {
-  const bool sh = x <= 5.0;
-  const double q = ((((((x + 15.0) * x + 85.0) * x + 225.0) * x + 274.0) * x + 120.0) * x);
-  const double p = (((((6.0 * x + 75.0) * x + 340.0) * x + 675.0) * x + 548.0) * x + 120.0);
-  const double iq = rcp_nr(sh ? q : 1.0);
-  double c = p * iq;
-  c = fma(fma(-q, c, p), iq, c);  // one residual correction of p/q
-  const double y = sh ? x + 6.0 : x;
-  const double iy = rcp_nr(y);
-  const double f = iy * iy;
-  const double t = f * (-1.0 / 12.0 + f * (1.0 / 120.0 + f * (-1.0 / 252.0 + f * (1.0 / 240.0 +
-                   f * (-1.0 / 132.0 + f * (691.0 / 32760.0 + f * (-1.0 / 12.0 + f * (3617.0 / 8160.0))))))));
-  return (sh ? breeze_shift_fix(x, iy, sh) - c : 0.0) + log(y) - 0.5 * iy + t;
-}
-// exp(ψ(x) − cst) for the fp64 E-step's eθ = exp(ψ(γ) − ψ(Σγ)), without the logarithm: with ψ(x) =
-// ln y − 0.5/y + t(y) − s(x) as in digamma_fast_d, exp(ψ(x) − cst) = y · exp(t − 0.5/y − s − cst).
-__device__ inline double exp_digamma_minus_d(double x, double cst) {
-  const bool sh = x <= 5.0;
-  const double q = ((((((x + 15.0) * x + 85.0) * x + 225.0) * x + 274.0) * x + 120.0) * x);
-  const double p = (((((6.0 * x + 75.0) * x + 340.0) * x + 675.0) * x + 548.0) * x + 120.0);
-  const double iq = rcp_nr(sh ? q : 1.0);
-  double c = p * iq;
-  c = fma(fma(-q, c, p), iq, c);
-  const double y = sh ? x + 6.0 : x;
-  const double iy = rcp_nr(y);
-  const double f = iy * iy;
-  const double t = f * (-1.0 / 12.0 + f * (1.0 / 120.0 + f * (-1.0 / 252.0 + f * (1.0 / 240.0 +
-                   f * (-1.0 / 132.0 + f * (691.0 / 32760.0 + f * (-1.0 / 12.0 + f * (3617.0 / 8160.0))))))));
-  return y * exp(((sh ? breeze_shift_fix(x, iy, sh) - c : 0.0) - 0.5 * iy + t) - cst);
-}
-
-__host__ __device__ inline double trigamma_d(double x) {
-  double r = 0;
-  while (x <= 5.0) {
-    r += 1.0 / (x * x);
-    x += 1.0;
-  }
-  const double f = 1.0 / (x * x);
-  const double t = f * (1 / 6.0 + f * (-1 / 30.0 + f * (1 / 42.0 + f * (-1 / 30.0 + f * (5 / 66.0 +
-                   f * (-691 / 2730.0 + f * (7 / 6.0 - f * 3617 / 510.0)))))));
-  return r + 1.0 / x + f / 2.0 + t / x;
-}
-
-// ---------------------------------------------------------------------------------------
-// Wave64 / block reductions
-// ---------------------------------------------------------------------------------------
-// fp32 wave64 all-reduce without LDS: two permlane swaps (across 32 / 16 lanes) and four DPP
-// involutions inside each 16-lane row (row_mirror, row_half_mirror, quad_perm 1032 and 2301).
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  // all-lanes-valid permutations only (mirrors, quad_perm): bound_ctrl never fires, no `old` operand
-  return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// v_readlane of a float / double (wave-uniform lane index)
-__device__ __forceinline__ float readlane_t(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ double readlane_t(double v, int l) {
-  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-// max of two non-negative floats as an unsigned compare of their bits (no NaN canonicalisation)
-__device__ __forceinline__ float max_nonneg(float a, float b) {
-  return __builtin_bit_cast(float, max(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b)));
-}
-// Compiler hazard (ROCm 7.2 hipcc, gfx950): with __builtin_amdgcn_permlane{16,32}_swap the compiler
-// sometimes reads the FIRST result register for both results (`v_add v0, v0, v0` after the swap;
-// seen whenever both operands carry the same value, even through an opaque copy).  The swaps are
-// therefore issued as inline asm with both registers in/out; `s_nop 1` covers the VALU-write →
-// permlane-read hazard the compiler inserts for the builtin.  `volatile` keeps the compiler from
-// re-materialising a swap inside a divergent branch (inactive partner lanes ⇒ garbage).
-__device__ __forceinline__ void pswap32(unsigned& x, unsigned& y) {
-  asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-__device__ __forceinline__ void pswap16(unsigned& x, unsigned& y) {
-  asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-}
-__device__ __forceinline__ float swap32_pair(float v, bool add, float w) {
-  unsigned x = __builtin_bit_cast(unsigned, v), y = __builtin_bit_cast(unsigned, w);
-  pswap32(x, y);
-  const float a = __builtin_bit_cast(float, x), b = __builtin_bit_cast(float, y);
-  return add ? a + b : fmaxf(a, b);
-}
-__device__ __forceinline__ float swap16_pair(float v, bool add, float w) {
-  unsigned x = __builtin_bit_cast(unsigned, v), y = __builtin_bit_cast(unsigned, w);
-  pswap16(x, y);
-  const float a = __builtin_bit_cast(float, x), b = __builtin_bit_cast(float, y);
-  return add ? a + b : fmaxf(a, b);
-}
-// Batched swaps: up to four independent swaps behind one hazard nop.
-template <bool D32>
-__device__ __forceinline__ void pswap_4(unsigned& a0, unsigned& b0, unsigned& a1, unsigned& b1, unsigned& a2,
-                                        unsigned& b2, unsigned& a3, unsigned& b3) {
-  if constexpr (D32)
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3\n\t"
-                 "v_permlane32_swap_b32 %4, %5\n\tv_permlane32_swap_b32 %6, %7"
-                 : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3));
-  else
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3\n\t"
-                 "v_permlane16_swap_b32 %4, %5\n\tv_permlane16_swap_b32 %6, %7"
-                 : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1), "+v"(a2), "+v"(b2), "+v"(a3), "+v"(b3));
-}
-template <bool D32>
-__device__ __forceinline__ void pswap_2(unsigned& a0, unsigned& b0, unsigned& a1, unsigned& b1) {
-  if constexpr (D32)
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\tv_permlane32_swap_b32 %2, %3"
-                 : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1));
-  else
-    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\tv_permlane16_swap_b32 %2, %3"
-                 : "+v"(a0), "+v"(b0), "+v"(a1), "+v"(b1));
-}
-template <bool D32>
-__device__ __forceinline__ void pswap_1(unsigned& a0, unsigned& b0) {
-  if constexpr (D32) pswap32(a0, b0);
-  else pswap16(a0, b0);
-}
-// reduce-scatter step over lane distance 32 (D32) or 16, N pairs: lanes with the role bit clear
-// keep the xs set, the others the ys set; out[i] = this lane's kept value + the partner's
-template <bool D32, int N>
-__device__ __forceinline__ void swap_add_n(const float* xs, const float* ys, float* out) {
-  unsigned x[N], y[N];
-#pragma unroll
-  for (int i = 0; i < N; ++i) {
-    x[i] = __builtin_bit_cast(unsigned, xs[i]);
-    y[i] = __builtin_bit_cast(unsigned, ys[i]);
-  }
-  constexpr int N4 = N / 4 * 4;
-#pragma unroll
-  for (int b = 0; b < N4; b += 4) pswap_4<D32>(x[b], y[b], x[b + 1], y[b + 1], x[b + 2], y[b + 2], x[b + 3], y[b + 3]);
-  if constexpr (N - N4 >= 2) pswap_2<D32>(x[N4], y[N4], x[N4 + 1], y[N4 + 1]);
-  if constexpr ((N - N4) % 2 == 1) pswap_1<D32>(x[N - 1], y[N - 1]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) out[i] = __builtin_bit_cast(float, x[i]) + __builtin_bit_cast(float, y[i]);
-}
-// three wave all-reduces at once (Σ a, Σ b, max c ≥ 0): the swaps share their hazard nops
-__device__ __forceinline__ void wave_reduce3(float& a, float& b, float& c) {
-  {
-    unsigned a0 = __builtin_bit_cast(unsigned, a), a1 = a0, b0 = __builtin_bit_cast(unsigned, b), b1 = b0,
-             c0 = __builtin_bit_cast(unsigned, c), c1 = c0, d0 = 0, d1 = 0;
-    pswap_4<true>(a0, a1, b0, b1, c0, c1, d0, d1);
-    a = __builtin_bit_cast(float, a0) + __builtin_bit_cast(float, a1);
-    b = __builtin_bit_cast(float, b0) + __builtin_bit_cast(float, b1);
-    c = max_nonneg(__builtin_bit_cast(float, c0), __builtin_bit_cast(float, c1));
-  }
-  {
-    unsigned a0 = __builtin_bit_cast(unsigned, a), a1 = a0, b0 = __builtin_bit_cast(unsigned, b), b1 = b0,
-             c0 = __builtin_bit_cast(unsigned, c), c1 = c0, d0 = 0, d1 = 0;
-    pswap_4<false>(a0, a1, b0, b1, c0, c1, d0, d1);
-    a = __builtin_bit_cast(float, a0) + __builtin_bit_cast(float, a1);
-    b = __builtin_bit_cast(float, b0) + __builtin_bit_cast(float, b1);
-    c = max_nonneg(__builtin_bit_cast(float, c0), __builtin_bit_cast(float, c1));
-  }
-  a += dpp_f<0x140>(a);
-  b += dpp_f<0x140>(b);
-  c = max_nonneg(c, dpp_f<0x140>(c));
-  a += dpp_f<0x141>(a);
-  b += dpp_f<0x141>(b);
-  c = max_nonneg(c, dpp_f<0x141>(c));
-  a += dpp_f<0xB1>(a);
-  b += dpp_f<0xB1>(b);
-  c = max_nonneg(c, dpp_f<0xB1>(c));
-  a += dpp_f<0x4E>(a);
-  b += dpp_f<0x4E>(b);
-  c = max_nonneg(c, dpp_f<0x4E>(c));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-  v = swap32_pair(v, true, v);
-  v = swap16_pair(v, true, v);
-  v += dpp_f<0x140>(v);  // row_mirror
-  v += dpp_f<0x141>(v);  // row_half_mirror
-  v += dpp_f<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f<0x4E>(v);   // quad_perm [2,3,0,1]
-  return v;
-}
-__device__ __forceinline__ float wave_max_dpp(float v) {
-  v = swap32_pair(v, false, v);
-  v = swap16_pair(v, false, v);
-  v = fmaxf(v, dpp_f<0x140>(v));
-  v = fmaxf(v, dpp_f<0x141>(v));
-  v = fmaxf(v, dpp_f<0xB1>(v));
-  v = fmaxf(v, dpp_f<0x4E>(v));
-  return v;
-}
-
-template <typename R>
-__device__ inline R wave_sum(R v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-template <typename R>
-__device__ inline R wave_max(R v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

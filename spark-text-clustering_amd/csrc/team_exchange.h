@@ -92,7 +92,7 @@ using team::team_sum;
 // handler → libhsa-runtime64, on a /dev/dri mapping already released).  Residency is checked here; a
 // block that is nonetheless not co-resident (another process on the device) only delays its team, and
 // the bounded spins turn a delay past the limit into a timeout word, on which the host re-runs the
-// same slots on the one-CU kernel (api.hip launch_split).
+// same slots on the one-CU kernel (lda_online.hip launch_split).
 inline bool launch_resident(const void* kern, int blocks, int threads, size_t lds, void** args, hipStream_t s) {
   int dev = 0, cus = 0, per_cu = 0;
   HIP_CHECK(hipGetDevice(&dev));

@@ -1,4 +1,4 @@
-"""Accuracy of the E-step's fp32 digamma (stc_internal.h digamma_fast) against scipy, in numpy fp32.
+"""Accuracy of the E-step's fp32 digamma (estep_common.h digamma_fast) against scipy, in numpy fp32.
 
     python tools/dg_check.py
 """

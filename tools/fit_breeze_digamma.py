@@ -4,7 +4,7 @@ recurrence while x ≤ 5, then S8).  The device digamma evaluates S8 at x + 6 (o
 recurrence terms); adding E(x + 6) − E(y_B) at y_B = x + ⌊5 − x⌋ + 1 reproduces Breeze's value to
 ~1e-16 instead of differing from it by up to 8e-13 (which a slowly-dying topic of a long E-step
 amplifies past 1e-7).  E(y)·y^18 is fitted as a polynomial in f = 1/y² over y ∈ [5, 11.5] with
-mpmath at 50 digits.  Prints the C initialiser for csrc/stc_internal.h."""
+mpmath at 50 digits.  Prints the C initialiser for csrc/estep_common.h."""
 import mpmath as mp
 import numpy as np
 

@@ -28,7 +28,7 @@ sys.path.insert(0, ROOT)
 
 # kernels of the E-step phase (the bench roofline's "kernel"): E-step, term sort, sstats SpMM,
 # the stat memset, and the partition scans (rocprim; tiny)
-PHASE = re.compile(r"k_estep|k_sstats|k_fixup|rocprim|fillBuffer|k_part_|k_fill_batch|k_batch_nnz|k_mixed_|k_entry_pairs")
+PHASE = re.compile(r"k_estep|k_sstats|k_fixup|rocprim|fillBuffer|k_part_|k_fill_batch|k_mixed_|k_entry_pairs")
 # bench.py's roofline window (SURVEY §8(d) K6 = gather + scatter): the training E-step launches and the
 # sstats phase after them — the stat clear, the (term, slot) radix sort, k_sstats / k_fixup, logphat and the
 # iteration statistics (HIP events 1 → 3 in lda_online.hip estep_and_stats)
