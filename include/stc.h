@@ -33,6 +33,7 @@
  *   stc_em_*                    [U] EMLDAOptimizer, the reference's default optimizer ("em", Params.scala:9) —
  *                               LDAClustering.scala:41; stc_em_log_likelihood is
  *                               DistributedLDAModel.logLikelihood / logPrior — LDAClustering.scala:75
+ *   stc_em_topic_assignments    [U] DistributedLDAModel.topicAssignments (the model LDALoader.scala:37 loads)
  *   stc_comm_*                  the role of Spark's broadcast + treeReduce inside lda.run
  *                               (per minibatch: RCCL reduce-scatter of the k×V sstats over
  *                               vocabulary slices, the slice's λ update, all-gather of expElogβ)
@@ -433,6 +434,13 @@ int stc_em_next(stc_em* em, int32_t n_iterations);
  * θ_d = (N_dk[d] + α−1) normalised; logPrior = (η−1) Σ_terms Σ_j ln φ_w[j] + (α−1) Σ_docs Σ_j ln θ_d[j] over
  * the vertices that exist.  Either may be NULL.  STC_ERR_STATE without a state. */
 int stc_em_log_likelihood(stc_em* em, double* log_likelihood_out, double* log_prior_out);
+/* DistributedLDAModel.topicAssignments under the current state: for every edge, in the filtered graph's CSR
+ * order, the topic j maximising (N_wk[w][j] + η−1)(N_dk[d][j] + α−1) / (N_k[j] + V(η−1)), formed as
+ * stc_em_next forms it; ties go to the smallest j.  indptr_out int64[D+1] (a document without an edge has an
+ * empty range), terms_out int32[E] (ascending inside a document), topics_out int32[E]; E from stc_em_shape;
+ * any may be NULL.  Waits for queued iterations (with all three NULL the pass is only enqueued, as an
+ * iteration is: nothing is copied, so there is nothing to wait for).  STC_ERR_STATE without a state. */
+int stc_em_topic_assignments(stc_em* em, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out);
 
 /* ---- one process, N devices ---------------------------------------------------------------
  * The reference trains in ONE JVM (Spark local[*], LDATraining.scala:7), so its drop-in drives every GPU

@@ -683,6 +683,23 @@ JNIEXPORT jdoubleArray JNICALL FN(emLogLikelihood)(JNIEnv* env, jclass c, jlong 
   return out;
 }
 
+/* every array nullable: indptr nDocs + 1, terms nEdges, topics nEdges */
+JNIEXPORT void JNICALL FN(emTopicAssignments)(JNIEnv* env, jclass c, jlong em, jlongArray indptr, jintArray terms,
+                                              jintArray topics) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (em_shape(env, em, s) || NEED(indptr, s[1] + 1, "emTopicAssignments indptr") ||
+      NEED(terms, s[3], "emTopicAssignments terms") || NEED(topics, s[3], "emTopicAssignments topics"))
+    return;
+  jlong* ip = PIN(jlong, Long, indptr);
+  jint* te = PIN(jint, Int, terms);
+  jint* to = PIN(jint, Int, topics);
+  int st = stc_em_topic_assignments(EM(em), (int64_t*)ip, (int32_t*)te, (int32_t*)to);
+  UNPIN(Int, topics, to, 0);
+  UNPIN(Int, terms, te, 0);
+  UNPIN(Long, indptr, ip, 0);
+  check(env, st);
+}
+
 /* ---- CountVectorizer (stc_cv_*: ml.feature.CountVectorizer / CountVectorizerModel) ---------------- */
 JNIEXPORT jlong JNICALL FN(cvFit)(JNIEnv* env, jclass c, jlong ctx, jbyteArray utf8, jlongArray tok_off,
                                   jlongArray doc_off, jlong vocab_size, jdouble min_df, jdouble max_df) {

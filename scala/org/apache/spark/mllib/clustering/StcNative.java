@@ -121,6 +121,9 @@ public final class StcNative {
   public static native void emNext(long em, int nIterations);
   /** {logLikelihood, logPrior} */
   public static native double[] emLogLikelihood(long em);
+  /** DistributedLDAModel.topicAssignments: per edge in CSR order the first topic with the largest factor; every
+   *  array nullable: indptr nDocs + 1, terms nEdges (ascending per document), topics nEdges */
+  public static native void emTopicAssignments(long em, long[] indptr, int[] terms, int[] topics);
 
   // ---- CountVectorizer (stc_cv_*: ml.feature.CountVectorizer / CountVectorizerModel; tokens as for HashingTF)
   /** fit: the vocabSize most frequent terms with minDf <= df <= maxDf (ties by the terms' UTF-8 bytes) */

@@ -8,7 +8,8 @@
 // The graph never changes, so create() builds it once in both orientations (the filtered CSR and its
 // transpose by a stable radix sort) and an iteration is the same kernel run twice: over rows (→ N_dk',
 // gathering N_wk rows) and over columns (→ N_wk', gathering N_dk rows).  Each run recomputes γ; the E×k
-// messages are never stored.
+// messages are never stored.  logLikelihood and topicAssignments are the row run in further modes (a scalar
+// per chunk; per edge the first topic with the largest γ).
 //
 // Reproducibility: no float atomics.  A vertex's edge list is cut into chunks of kChunk edges; one wave
 // sums one chunk (topics across lanes; for k < 64 several edges side by side, folded in a fixed lane
@@ -54,7 +55,7 @@ struct SideView {
   int64_t n_chunks;
 };
 
-enum Mode { kUpdate = 0, kLogLik = 1, kInit = 2 };
+enum Mode { kUpdate = 0, kLogLik = 1, kInit = 2, kAssign = 3 };
 
 struct PassArgs {
   SideView g;
@@ -67,11 +68,14 @@ struct PassArgs {
   double* scalar;       // kLogLik: one value per chunk
   uint64_t seed;        // kInit
   int k;
+  int32_t* assign;      // kAssign: E, one topic per edge (rows only: the edge's position is its CSR position)
 };
 
 // Topics across lanes.  KP < 64: 64/KP edges side by side (lane = edge slot × KP + topic), the normalising
 // sum a reduction over KP lanes.  KP = 64: NS slices of 64 topics per lane.  The product own·other is the
 // same number in both orientations (one rounding, commutative), so both passes see the same γ.
+// kAssign (rows only) keeps no sum: per edge the first j with the largest factor, the factor formed as kUpdate
+// forms it.  A padding lane or an empty slot carries −1, below every real factor (α, η > 1 make them > 0).
 template <int KP, int NS, int MODE>
 __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
   const int lane = threadIdx.x & 63;
@@ -106,6 +110,33 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
     const int64_t ed = base + slot;
     const bool valid = ed < e;
     const int64_t o = valid ? (int64_t)a.g.idx[ed] : 0;
+    if (MODE == kAssign) {
+      // every lane loads (a padding lane the last topic, an empty slot row 0), so the NS loads issue together
+      const double* row = a.other + o * k;
+      double x[NS];
+#pragma unroll
+      for (int i = 0; i < NS; ++i) x[i] = row[min(j0 + 64 * i, k - 1)];
+      double best = -1.0;
+      int bj = j0;
+#pragma unroll
+      for (int i = 0; i < NS; ++i) {  // ascending j, strict >: the first maximum of this lane
+        const int j = j0 + 64 * i;
+        const double gi = (valid && j < k) ? (own[i] * (x[i] + a.other_add)) * inv[i] : -1.0;
+        const bool up = gi > best;
+        best = up ? gi : best;
+        bj = up ? j : bj;
+      }
+#pragma unroll
+      for (int off = KP / 2; off > 0; off >>= 1) {  // the slot's lanes: larger value, then smaller index
+        const double ov = __shfl_xor(best, off, 64);
+        const int oj = __shfl_xor(bj, off, 64);
+        const bool take = (ov > best) | ((ov == best) & (oj < bj));
+        best = take ? ov : best;
+        bj = take ? oj : bj;
+      }
+      if (valid && j0 == 0) a.assign[ed] = bj;
+      continue;
+    }
     const double cn = valid ? a.g.cnt[ed] : 0.0;
     double g[NS], sum = 0.0;
     if (MODE == kInit) {
@@ -134,6 +165,7 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
       for (int i = 0; i < NS; ++i) acc[i] += w * g[i];
     }
   }
+  if (MODE == kAssign) return;
   // fold the edge slots (fixed order), slot 0 holds the chunk's sum
   if (MODE == kLogLik) {
 #pragma unroll
@@ -399,6 +431,7 @@ struct stc_em {
   DevBuf sum_part;       // first-level partials of the N_k and scalar reductions
   DevBuf scalar;         // per-chunk / per-vertex scalars of logLikelihood / logPrior
   DevBuf result;         // 3 doubles: Σ c ln(φ·θ), Σ ln φ, Σ ln θ
+  DevBuf assign;         // int32[E]: topicAssignments' output (allocated by its first call)
 };
 
 namespace stc {
@@ -462,8 +495,9 @@ void run_side(stc_em& m, bool row_side, int from, int to, uint64_t seed) {
   a.scalar = m.scalar.as<double>();
   a.seed = seed;
   a.k = m.k;
+  a.assign = m.assign.as<int32_t>();
   launch_pass<MODE>(s, a);
-  if (MODE != kLogLik && g.n > 0) {
+  if (MODE != kLogLik && MODE != kAssign && g.n > 0) {
     k_em_fixup<<<strided_blocks(g.n * m.k), 256, 0, s>>>(g.choff.as<int64_t>(), g.moff.as<int64_t>(),
                                                         m.partial.as<double>(), out, g.n, m.k);
     KERNEL_CHECK();
@@ -685,6 +719,20 @@ void log_likelihood(stc_em& m, double* ll_out, double* prior_out) {
   if (prior_out) *prior_out = (m.eta - 1.0) * h[1] + (m.alpha - 1.0) * h[2];
 }
 
+void topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out) {
+  require_idle_single(*m.ctx);
+  if (!m.has_state) throw Error(STC_ERR_STATE, "em: no state yet (stc_em_init_random or stc_em_set_state first)");
+  m.ctx->use();
+  hipStream_t s = m.ctx->stream;
+  m.assign.reserve(4 * std::max<int64_t>(m.E, 1));
+  run_side<kAssign>(m, true, m.cur, m.cur, 0);
+  if (!indptr_out && !terms_out && !topics_out) return;  // enqueued like an iteration: nothing to wait for
+  if (indptr_out) HIP_CHECK(hipMemcpyAsync(indptr_out, m.rows.ptr.p, 8 * (m.D + 1), hipMemcpyDeviceToHost, s));
+  if (terms_out && m.E) HIP_CHECK(hipMemcpyAsync(terms_out, m.rows.idx.p, 4 * m.E, hipMemcpyDeviceToHost, s));
+  if (topics_out && m.E) HIP_CHECK(hipMemcpyAsync(topics_out, m.assign.p, 4 * m.E, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
 void shape(const stc_em& m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges) {
   if (k) *k = m.k;
   if (n_docs) *n_docs = m.D;
@@ -752,6 +800,13 @@ int stc_em_log_likelihood(stc_em* m, double* log_likelihood_out, double* log_pri
   return guard([&] {
     STC_REQUIRE(m, "em");
     em::log_likelihood(*m, log_likelihood_out, log_prior_out);
+  });
+}
+
+int stc_em_topic_assignments(stc_em* m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::topic_assignments(*m, indptr_out, terms_out, topics_out);
   });
 }
 

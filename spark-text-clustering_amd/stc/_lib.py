@@ -149,6 +149,7 @@ SIGNATURES = {
     "stc_em_get_state": (_int, [_p, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
     "stc_em_next": (_int, [_p, _i32]),
     "stc_em_log_likelihood": (_int, [_p, _pdbl, _pdbl]),
+    "stc_em_topic_assignments": (_int, [_p, _pi64, _pi32, _pi32]),
     "stc_group_create": (_int, [_pi32, _int, C.POINTER(LdaConfig), C.POINTER(_p)]),
     "stc_group_destroy": (_int, [_p]),
     "stc_group_size": (_int, [_p, _pi32]),

@@ -409,6 +409,16 @@ class EmHandle:
         L.check(self.ctx.lib.stc_em_log_likelihood(self.handle, C.byref(ll), C.byref(lp)))
         return ll.value, lp.value
 
+    def topic_assignments(self):
+        """(indptr int64[D+1], terms int32[E], topics int32[E]): per edge of the filtered graph, in CSR order,
+        the first topic with the largest factor under the current state; waits for queued iterations"""
+        indptr = np.zeros(self.num_docs + 1, np.int64)
+        terms = np.zeros(self.num_edges, np.int32)
+        topics = np.zeros(self.num_edges, np.int32)
+        L.check(self.ctx.lib.stc_em_topic_assignments(self.handle, L.ptr(indptr, C.c_int64), L.ptr(terms, C.c_int32),
+                                                      L.ptr(topics, C.c_int32)))
+        return indptr, terms, topics
+
     def close(self):
         if self.handle:
             self.ctx.lib.stc_em_destroy(self.handle)
@@ -519,7 +529,7 @@ class DistributedLDAModel:
 
     It is also what ``MllibLDA.run`` returns under the EM optimizer (LDAClustering.scala:41, :61-63): the
     trained graph's state read back from its ``EmHandle``.  ``logLikelihood`` / ``logPrior``
-    (LDAClustering.scala:75) run on the GPU; a loaded model builds its ``EmHandle`` from the stored edges
+    (LDAClustering.scala:75) and ``topicAssignments`` run on the GPU; a loaded model builds its ``EmHandle`` from the stored edges
     and state on first use, so the reference's own saved models can be scored."""
 
     def __init__(self, data, em: "EmHandle | None" = None):
@@ -531,6 +541,7 @@ class DistributedLDAModel:
         self.iterationTimes = data["iteration_times"]
         self._local = {}
         self._em = em
+        self._em_rows_are_ids = em is not None  # the trainer's graph: row = document id; a rebuilt one: its rank
 
     @staticmethod
     def _from_em(em: "EmHandle", corpus: CsrMatrix, iteration_times, gamma_shape=100.0) -> "DistributedLDAModel":
@@ -577,6 +588,18 @@ class DistributedLDAModel:
     def logPrior(self, ctx: Context | None = None):
         """[U] DistributedLDAModel.logPrior: ln P(topics, topic distributions | α, η) up to its constant"""
         return self._em_handle(ctx).log_likelihood()[1]
+
+    def topicAssignments(self, ctx: Context | None = None):
+        """[U] DistributedLDAModel.topicAssignments: [(document id, terms int32[], topics int32[])], one entry
+        per document vertex in ``topicDistributions``' order; per (document, term) edge, terms ascending, the
+        first topic with the largest (N_wk[w][j] + η−1)(N_dk[d][j] + α−1) / (N_k[j] + V(η−1)), on the GPU"""
+        indptr, terms, topics = self._em_handle(ctx).topic_assignments()
+        ids = self._d["doc_ids"]
+        rows = ids if self._em_rows_are_ids else np.arange(ids.size)
+        return [(int(d), terms[indptr[r]:indptr[r + 1]].copy(), topics[indptr[r]:indptr[r + 1]].copy())
+                for d, r in zip(ids, rows)]
+
+    javaTopicAssignments = topicAssignments
 
     def topicDistributions(self):
         """(document ids, D'×k matrix): N_dk[d] / Σ_j N_dk[d][j] for every document vertex"""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the EM optimizer's iteration (stc_em_next) — one JSON line per case.
+"""Time the EM optimizer's iteration (stc_em_next) and its topicAssignments pass — one JSON line per case.
 
 Cases:
   golden   the reference's saved EN model's graph (tests/golden/LdaModel_EN_1591049082850: 51 documents,
@@ -14,7 +14,13 @@ median and the spread.  edges·k per second and algorithmic bytes per second fol
 Algorithmic bytes per iteration = for each of the two passes, the edge arrays once (4 B index + 8 B count
 per edge) plus one gathered k-row (8k B) per edge: 2·E·(12 + 8k).
 
-    python tools/bench_em.py [--case golden|zipf|all] [--iters 20] [--warmup 3] [--repeats 5]
+The topicAssignments pass (stc_em_topic_assignments with every output NULL: the pass is enqueued, nothing is
+copied out) is timed in the same run under the same discipline, from the state the timed iterations left:
+--warmup untimed passes, --iters passes as one enqueued batch, --repeats times.  Its algorithmic bytes are the
+term index, one gathered k-row and the 4 B result per edge: E·(8 + 8k).  The row pass it is to be read
+against is one kernel of the iteration; its time comes from a kernel trace of this tool's run.
+
+    python tools/bench_em.py [--case golden|zipf|all] [--iters 20] [--warmup 3] [--repeats 5] [--workers N]
 """
 import argparse
 import json
@@ -47,15 +53,34 @@ def golden_case(stc, ctx):
                "reference_note": "median of the saved model's 50 iterationTimes; unknown PC, Spark local[*]"}
 
 
-def zipf_case(stc, ctx, docs, tokens, vocab, k):
+def zipf_case(stc, ctx, docs, tokens, vocab, k, workers):
     from stc import synth
 
-    corpus = synth.zipf_corpus(docs, tokens, vocab, workers=min(16, os.cpu_count() or 1))
+    corpus = synth.zipf_corpus(docs, tokens, vocab, workers=workers)
     dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
     h = stc.EmHandle(ctx, dev, k)
     dev.free()
     h.init_random(1)
     return h, {"case": "zipf", "docs": docs, "tokens_per_doc": tokens}
+
+
+def assign_pass_ms(ctx, h, iters, warmup, repeats):
+    """ms per topicAssignments pass without the copy-out, per repeat"""
+    from stc import _lib as L
+
+    def enqueue(n):
+        for _ in range(n):
+            L.check(ctx.lib.stc_em_topic_assignments(h.handle, None, None, None))
+
+    enqueue(warmup)
+    ctx.synchronize()
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        enqueue(iters)
+        ctx.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3 / iters)
+    return ms
 
 
 def measure(ctx, h, info, iters, warmup, repeats):
@@ -71,10 +96,14 @@ def measure(ctx, h, info, iters, warmup, repeats):
     E, k = h.num_edges, h.k
     algo_bytes = 2.0 * E * (12 + 8 * k)
     ll, lp = h.log_likelihood()
+    ams = assign_pass_ms(ctx, h, iters, warmup, repeats)
+    amed = float(np.median(ams))
     out = dict(info, n_docs=h.num_docs, vocab=h.vocab_size, k=k, edges=E, iters=iters, warmup=warmup, repeats=repeats,
                ms_per_iteration=med, ms_per_iteration_min=float(min(ms)), ms_per_iteration_max=float(max(ms)),
                edges_k_per_s=E * k / (med * 1e-3), algorithmic_bytes_per_iteration=algo_bytes,
-               algorithmic_bytes_per_s=algo_bytes / (med * 1e-3), log_likelihood=ll, log_prior=lp)
+               algorithmic_bytes_per_s=algo_bytes / (med * 1e-3), log_likelihood=ll, log_prior=lp,
+               ms_per_assign_pass=amed, ms_per_assign_pass_min=float(min(ams)), ms_per_assign_pass_max=float(max(ams)),
+               assign_algorithmic_bytes_per_s=E * (8.0 + 8 * k) / (amed * 1e-3))
     if "reference_s_per_iteration" in info:
         out["speedup_vs_reference"] = info["reference_s_per_iteration"] / (med * 1e-3)
     return out
@@ -90,12 +119,14 @@ def main():
     p.add_argument("--tokens", type=int, default=200)
     p.add_argument("--vocab", type=int, default=1 << 18)
     p.add_argument("--k", type=int, default=100)
+    p.add_argument("--workers", type=int, default=min(16, os.cpu_count() or 1),
+                   help="corpus-generation processes of the zipf case (1 under a profiler: nothing is forked)")
     a = p.parse_args()
     import stc
 
     ctx = stc.Context.get(0)
     for case in (("golden", "zipf") if a.case == "all" else (a.case,)):
-        h, info = golden_case(stc, ctx) if case == "golden" else zipf_case(stc, ctx, a.docs, a.tokens, a.vocab, a.k)
+        h, info = golden_case(stc, ctx) if case == "golden" else zipf_case(stc, ctx, a.docs, a.tokens, a.vocab, a.k, a.workers)
         print(json.dumps(measure(ctx, h, info, a.iters, a.warmup, a.repeats)), flush=True)
         h.close()
 
