@@ -34,6 +34,8 @@
  *                               LDAClustering.scala:41; stc_em_log_likelihood is
  *                               DistributedLDAModel.logLikelihood / logPrior — LDAClustering.scala:75
  *   stc_em_topic_assignments    [U] DistributedLDAModel.topicAssignments (the model LDALoader.scala:37 loads)
+ *   stc_em_group_*              the same optimizer over the node's GPUs from one process: documents sharded
+ *                               as Spark partitions them, the term side summed (its aggregateMessages)
  *   stc_comm_*                  the role of Spark's broadcast + treeReduce inside lda.run
  *                               (per minibatch: RCCL reduce-scatter of the k×V sstats over
  *                               vocabulary slices, the slice's λ update, all-gather of expElogβ)
@@ -407,7 +409,8 @@ int stc_lda_kernel_counts(stc_lda* lda, int64_t out[12]);
  * all reads from the old state; a vertex's new counts are the sum of the messages of its edges.
  * α (symmetric) and η: −1 picks Spark's EM defaults 50/k + 1 and 1.1; anything else must be > 1.
  * 2 <= k <= 1024.  The results are bitwise reproducible (no float atomics; fixed summation orders).
- * Single device: every call on a context connected to other ranks returns STC_ERR_STATE.       */
+ * Single device: every call on a context connected to other ranks returns STC_ERR_STATE (several devices:
+ * stc_em_group, below).                                                                          */
 typedef struct stc_em stc_em;
 /* builds the graph on the device (the filtered CSR and its transpose) from an STC_F64 `corpus` of ctx (an
  * STC_F32 one: STC_ERR_INVALID_ARG).  The handle copies what it needs and keeps no reference to `corpus`. */
@@ -494,6 +497,50 @@ int stc_group_bound(stc_group* g, int64_t n_rows, int64_t n_cols, const int64_t*
 int stc_group_topic_distribution(stc_group* g, int64_t n_rows, int64_t n_cols, const int64_t* indptr,
                                  const int32_t* indices, const double* values, uint64_t gamma_seed,
                                  int64_t doc_id_base, const double* gamma0, double* out /* rows×k */);
+
+/* ---- EM LDA, one process, N devices -------------------------------------------------------
+ * The EM optimizer of stc_em_* over the devices of an stc_group (the same device rules, transports,
+ * STC_GROUP_RCCL knob, member threads and failure handling; at most 16 members).  The corpus is given once,
+ * on the host, and sharded as stc_group_set_corpus shards it: contiguous document ranges balanced by entries.
+ * Member i holds an stc_em over its documents with all V columns.  N_dk stays on the member; N_wk, N_k are
+ * replicated.  One iteration on every member: the row pass over its documents (exact, local), the column pass
+ * over its own edges (a term without a local edge: a 0 row), one all-reduce of N_wk' (V×k fp64), then N_k'.
+ * What is global: the RNG keys of init_random are the edges' positions in the whole corpus's CSR order, and a
+ * term has a vertex iff any member has an edge of it.  Document ids, rows of doc_topics and the order of
+ * topicAssignments are the whole corpus's.
+ * Against a single stc_em only the summation order of N_wk differs (per member, then over the members): N_dk'
+ * of one step from an injected state is bitwise the single handle's, a one-member group is bitwise an stc_em.
+ * With the in-process transport the members' sum runs in member order, so the replicas are bitwise equal and a
+ * run is bitwise reproducible for a given member count.
+ * Argument checks and error codes are stc_em_create's; a member with no documents or no edges is valid. */
+typedef struct stc_em_group stc_em_group;
+/* the host CSR (values double; entries of value 0 are not edges) is copied: nothing of it is kept */
+int stc_em_group_create(const int* device_ids, int n_devices, int64_t n_rows, int64_t n_cols, const int64_t* indptr,
+                        const int32_t* indices, const double* values, int32_t k, double doc_concentration,
+                        double topic_concentration, stc_em_group** out);
+int stc_em_group_destroy(stc_em_group* g);
+int stc_em_group_size(const stc_em_group* g, int* n_out);
+int stc_em_group_transport(const stc_em_group* g, int* transport_out); /* enum stc_transport */
+/* of the whole corpus; any may be NULL */
+int stc_em_group_shape(const stc_em_group* g, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges);
+/* member i's handle and its first corpus row (may be NULL), for reading only: stc_em_shape and stc_em_get_state
+ * (the member's own N_dk rows, its replica of N_wk and N_k).  Every other stc_em_* call on a member of a group
+ * with a communicator returns STC_ERR_STATE. */
+int stc_em_group_member(stc_em_group* g, int i, stc_em** em_out, int64_t* row0_out);
+int stc_em_group_init_random(stc_em_group* g, uint64_t seed);
+/* doc_topics D×k (rows of the whole corpus), term_topics V×k */
+int stc_em_group_set_state(stc_em_group* g, const double* doc_topics, const double* term_topics);
+/* doc_topics D×k gathered from the members, term_topics V×k and totals k from member 0; any may be NULL */
+int stc_em_group_get_state(stc_em_group* g, double* doc_topics, double* term_topics, double* totals,
+                           double* alpha_out, double* eta_out);
+/* enqueues on every member; with an RCCL communicator it does not wait (stc_em_group_synchronize does), the
+ * in-process transport synchronises the host inside every all-reduce */
+int stc_em_group_next(stc_em_group* g, int32_t n_iterations);
+int stc_em_group_synchronize(stc_em_group* g);
+/* the members' edge and document sums added in member order, the term vertices counted once */
+int stc_em_group_log_likelihood(stc_em_group* g, double* log_likelihood_out, double* log_prior_out);
+/* as stc_em_topic_assignments, in the whole corpus's filtered CSR order: indptr_out int64[D+1] */
+int stc_em_group_topic_assignments(stc_em_group* g, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out);
 
 #ifdef __cplusplus
 }

@@ -1109,3 +1109,142 @@ JNIEXPORT void JNICALL FN(groupTopicDistribution)(JNIEnv* env, jclass c, jlong g
   UNPIN(Long, indptr, ip, JNI_ABORT);
   check(env, st);
 }
+
+/* ---- EM LDA, one process, N devices (stc_em_group) ------------------------------------------------- */
+#define EMG(h) ((stc_em_group*)(intptr_t)(h))
+static int emg_shape(JNIEnv* env, jlong g, int64_t s[4]) {
+  int32_t k = 0;
+  if (check(env, stc_em_group_shape(EMG(g), &k, &s[1], &s[2], &s[3]))) return 1;
+  s[0] = k;
+  return 0;
+}
+
+/* the host CSR is copied: nothing of the arrays is kept */
+JNIEXPORT jlong JNICALL FN(emGroupCreate)(JNIEnv* env, jclass c, jintArray devices, jlong rows, jlong cols,
+                                          jlongArray indptr, jintArray indices, jdoubleArray values, jint k,
+                                          jdouble alpha, jdouble eta) {
+  if (!devices || LEN(devices) < 1) {
+    throw_iae(env, "emGroupCreate: at least one device id");
+    return 0;
+  }
+  if (csr_args(env, rows, indptr, indices, values, "emGroupCreate")) return 0;
+  jint* dv = PIN(jint, Int, devices);
+  jlong* ip = PIN(jlong, Long, indptr);
+  jint* ix = PIN(jint, Int, indices);
+  jdouble* vs = PIN(jdouble, Double, values);
+  stc_em_group* out = NULL;
+  int st = stc_em_group_create((const int*)dv, (int)LEN(devices), rows, cols, (const int64_t*)ip, (const int32_t*)ix, vs,
+                               k, alpha, eta, &out);
+  UNPIN(Double, values, vs, JNI_ABORT);
+  UNPIN(Int, indices, ix, JNI_ABORT);
+  UNPIN(Long, indptr, ip, JNI_ABORT);
+  UNPIN(Int, devices, dv, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT void JNICALL FN(emGroupDestroy)(JNIEnv* env, jclass c, jlong g) { check(env, stc_em_group_destroy(EMG(g))); }
+
+JNIEXPORT jint JNICALL FN(emGroupSize)(JNIEnv* env, jclass c, jlong g) {
+  int n = 0;
+  check(env, stc_em_group_size(EMG(g), &n));
+  return n;
+}
+
+/* STC_TRANSPORT_NONE / _IN_PROCESS / _RCCL */
+JNIEXPORT jint JNICALL FN(emGroupTransport)(JNIEnv* env, jclass c, jlong g) {
+  int t = 0;
+  check(env, stc_em_group_transport(EMG(g), &t));
+  return t;
+}
+
+/* {k, nDocs, vocabSize, nEdges} of the whole corpus */
+JNIEXPORT jlongArray JNICALL FN(emGroupShape)(JNIEnv* env, jclass c, jlong g) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (emg_shape(env, g, s)) return NULL;
+  jlongArray out = (*env)->NewLongArray(env, 4);
+  if (out) (*env)->SetLongArrayRegion(env, out, 0, 4, (const jlong*)s);
+  return out;
+}
+
+/* {member i's stc_em (emShape / emGetState only), its first corpus row} */
+JNIEXPORT jlongArray JNICALL FN(emGroupMember)(JNIEnv* env, jclass c, jlong g, jint i) {
+  stc_em* m = NULL;
+  int64_t r[2] = {0, 0};
+  if (check(env, stc_em_group_member(EMG(g), i, &m, &r[1]))) return NULL;
+  r[0] = (int64_t)(intptr_t)m;
+  jlongArray out = (*env)->NewLongArray(env, 2);
+  if (out) (*env)->SetLongArrayRegion(env, out, 0, 2, (const jlong*)r);
+  return out;
+}
+
+JNIEXPORT void JNICALL FN(emGroupInitRandom)(JNIEnv* env, jclass c, jlong g, jlong seed) {
+  check(env, stc_em_group_init_random(EMG(g), (uint64_t)seed));
+}
+
+JNIEXPORT void JNICALL FN(emGroupSetState)(JNIEnv* env, jclass c, jlong g, jdoubleArray doc_topics,
+                                           jdoubleArray term_topics) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (emg_shape(env, g, s) || NEED(doc_topics, s[1] * s[0], "emGroupSetState docTopics") ||
+      NEED(term_topics, s[2] * s[0], "emGroupSetState termTopics"))
+    return;
+  jdouble* d = PIN(jdouble, Double, doc_topics);
+  jdouble* t = PIN(jdouble, Double, term_topics);
+  int st = stc_em_group_set_state(EMG(g), d, t);
+  UNPIN(Double, term_topics, t, JNI_ABORT);
+  UNPIN(Double, doc_topics, d, JNI_ABORT);
+  check(env, st);
+}
+
+/* every array nullable; alphaEta (2) receives the resolved docConcentration and topicConcentration */
+JNIEXPORT void JNICALL FN(emGroupGetState)(JNIEnv* env, jclass c, jlong g, jdoubleArray doc_topics,
+                                           jdoubleArray term_topics, jdoubleArray totals, jdoubleArray alpha_eta) {
+  int64_t s[4] = {0, 0, 0, 0};
+  double ae[2] = {0, 0};
+  if (emg_shape(env, g, s) || NEED(doc_topics, s[1] * s[0], "emGroupGetState docTopics") ||
+      NEED(term_topics, s[2] * s[0], "emGroupGetState termTopics") || NEED(totals, s[0], "emGroupGetState totals") ||
+      NEED(alpha_eta, 2, "emGroupGetState alphaEta"))
+    return;
+  jdouble* d = PIN(jdouble, Double, doc_topics);
+  jdouble* t = PIN(jdouble, Double, term_topics);
+  jdouble* n = PIN(jdouble, Double, totals);
+  int st = stc_em_group_get_state(EMG(g), d, t, n, &ae[0], &ae[1]);
+  UNPIN(Double, totals, n, 0);
+  UNPIN(Double, term_topics, t, 0);
+  UNPIN(Double, doc_topics, d, 0);
+  if (!check(env, st) && alpha_eta) (*env)->SetDoubleArrayRegion(env, alpha_eta, 0, 2, ae);
+}
+
+JNIEXPORT void JNICALL FN(emGroupNext)(JNIEnv* env, jclass c, jlong g, jint n_iterations) {
+  check(env, stc_em_group_next(EMG(g), n_iterations));
+}
+
+JNIEXPORT void JNICALL FN(emGroupSynchronize)(JNIEnv* env, jclass c, jlong g) {
+  check(env, stc_em_group_synchronize(EMG(g)));
+}
+
+/* {logLikelihood, logPrior} */
+JNIEXPORT jdoubleArray JNICALL FN(emGroupLogLikelihood)(JNIEnv* env, jclass c, jlong g) {
+  double r[2] = {0, 0};
+  if (check(env, stc_em_group_log_likelihood(EMG(g), &r[0], &r[1]))) return NULL;
+  jdoubleArray out = (*env)->NewDoubleArray(env, 2);
+  if (out) (*env)->SetDoubleArrayRegion(env, out, 0, 2, r);
+  return out;
+}
+
+/* every array nullable: indptr nDocs + 1, terms nEdges, topics nEdges */
+JNIEXPORT void JNICALL FN(emGroupTopicAssignments)(JNIEnv* env, jclass c, jlong g, jlongArray indptr, jintArray terms,
+                                                   jintArray topics) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (emg_shape(env, g, s) || NEED(indptr, s[1] + 1, "emGroupTopicAssignments indptr") ||
+      NEED(terms, s[3], "emGroupTopicAssignments terms") || NEED(topics, s[3], "emGroupTopicAssignments topics"))
+    return;
+  jlong* ip = PIN(jlong, Long, indptr);
+  jint* te = PIN(jint, Int, terms);
+  jint* to = PIN(jint, Int, topics);
+  int st = stc_em_group_topic_assignments(EMG(g), (int64_t*)ip, (int32_t*)te, (int32_t*)to);
+  UNPIN(Int, topics, to, 0);
+  UNPIN(Int, terms, te, 0);
+  UNPIN(Long, indptr, ip, 0);
+  check(env, st);
+}

@@ -208,4 +208,28 @@ public final class StcNative {
   public static native void groupTopicDistribution(long group, long rows, long cols, long[] indptr, int[] indices,
                                                    double[] values, long gammaSeed, long docIdBase,
                                                    double[] gamma0, double[] out);
+
+  // ---- EM LDA over N devices from one JVM (stc_em_group): documents sharded, the term side all-reduced ----
+  /** the host CSR is copied; docConcentration / topicConcentration −1 = auto; device rules as groupCreate */
+  public static native long emGroupCreate(int[] deviceIds, long rows, long cols, long[] indptr, int[] indices,
+                                          double[] values, int k, double docConcentration,
+                                          double topicConcentration);
+  public static native void emGroupDestroy(long emGroup);
+  public static native int emGroupSize(long emGroup);
+  public static native int emGroupTransport(long emGroup);
+  /** {k, nDocs, vocabSize, nEdges} of the whole corpus */
+  public static native long[] emGroupShape(long emGroup);
+  /** {member i's em handle (emShape / emGetState only), its first corpus row} */
+  public static native long[] emGroupMember(long emGroup, int i);
+  public static native void emGroupInitRandom(long emGroup, long seed);
+  public static native void emGroupSetState(long emGroup, double[] docTopics, double[] termTopics);
+  /** every array nullable: docTopics nDocs×k, termTopics vocabSize×k, totals k, alphaEta 2 */
+  public static native void emGroupGetState(long emGroup, double[] docTopics, double[] termTopics, double[] totals,
+                                            double[] alphaEta);
+  public static native void emGroupNext(long emGroup, int nIterations);
+  public static native void emGroupSynchronize(long emGroup);
+  /** {logLikelihood, logPrior} */
+  public static native double[] emGroupLogLikelihood(long emGroup);
+  /** every array nullable: indptr nDocs + 1, terms nEdges, topics nEdges, in the whole corpus's CSR order */
+  public static native void emGroupTopicAssignments(long emGroup, long[] indptr, int[] terms, int[] topics);
 }

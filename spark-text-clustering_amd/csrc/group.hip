@@ -4,159 +4,26 @@
 // of collectives.h when every member shares one device), N LDA handles over contiguous document shards (balanced by
 // entries), each call run on one host thread per member.  Built on the public ABI, collectives.h and the member
 // accessors of lda_online.h.
-#include <algorithm>
-#include <atomic>
 #include <cstdlib>
-#include <exception>
-#include <memory>
-#include <thread>
 
-#include "collectives.h"
+#include "group_common.h"
 #include "lda_online.h"
-#include "stc_handles.h"
 
 using namespace stc;
 
-struct stc_group {
-  std::vector<stc_ctx*> ctx;
+struct stc_group : GroupBase {
   std::vector<stc_lda*> lda;
   std::vector<stc_dcsr*> shard;
   std::vector<int64_t> row0;  // first corpus row of each member's shard (n + 1 entries)
-  std::unique_ptr<LocalColl> local;
   int64_t rows = 0, cols = 0, k = 0;  // the corpus's shape; the members' topic count
   int dtype = STC_F64;
-  int transport = STC_TRANSPORT_NONE;  // how the members' collectives travel (stc_group_transport)
-  bool threaded = false;               // run even a one-member call on its own host thread (STC_GROUP_RCCL)
-  // RCCL fault handling: a member's failure sets `abort` (every member's waits then throw instead of waiting
-  // on collectives the failed member never joins) and, after the call, aborts every member's communicator;
-  // the group is then `broken`: every later call but destroy fails with STC_ERR_STATE
-  std::atomic<bool> abort{false};
-  bool broken = false;
-  std::string broken_why;
-  int n() const { return (int)ctx.size(); }
 };
-
-namespace {
-
-void member_ok(int rc) {
-  if (rc != STC_OK) throw Error(rc, stc_last_error());
-}
-void require_usable(const stc_group& g) {
-  if (g.broken) throw Error(STC_ERR_STATE, "the group's RCCL communicator was aborted after a member failed (" +
-                                               g.broken_why + "): destroy the group and create a new one");
-}
-// f(i) for every member on its own thread (device set); the first failure is rethrown here.
-// In-process transport: a failure releases the members waiting in its barrier, and the group stays usable.
-// RCCL: a failure sets the group's abort flag, so every member's next wait throws instead of waiting for a
-// collective the failed member never enqueued; a member still blocked inside the runtime after a grace
-// period (a copy queued behind such a collective) has its communicator aborted by this thread, which
-// releases the collective's kernels; after the join every member's communicator is aborted and the group
-// is broken (STC_ERR_STATE from then on; stc_group_destroy returns).
-template <typename F>
-void for_members(stc_group& g, F f) {
-  require_usable(g);
-  const int n = g.n();
-  const bool rccl = g.transport == STC_TRANSPORT_RCCL;
-  std::vector<std::exception_ptr> err((size_t)n);
-  std::mutex fm;
-  std::condition_variable fcv;
-  int first = -1;  // the member that failed first (the others may only report "another member failed")
-  int running = n;
-  auto run = [&](int i) {
-    try {
-      g.ctx[(size_t)i]->use();
-      f(i);
-    } catch (...) {
-      err[(size_t)i] = std::current_exception();
-      {
-        std::lock_guard<std::mutex> lk(fm);
-        if (first < 0) first = i;
-      }
-      if (g.local) g.local->fail();  // release the members waiting in a barrier
-      if (rccl) g.abort.store(true);
-    }
-    std::lock_guard<std::mutex> lk(fm);
-    --running;
-    fcv.notify_all();
-  };
-  if (n == 1 && !g.threaded) {
-    run(0);
-  } else {
-    std::vector<std::thread> th;
-    th.reserve((size_t)n);
-    for (int i = 0; i < n; ++i) th.emplace_back(run, i);
-    if (rccl) {
-      std::unique_lock<std::mutex> lk(fm);
-      fcv.wait(lk, [&] { return running == 0 || first >= 0; });
-      if (running > 0 && !fcv.wait_for(lk, std::chrono::seconds(5), [&] { return running == 0; }))
-        for (auto* c : g.ctx) abort_comm(*c);  // members still blocked behind the failed member's collectives
-    }
-    for (auto& t : th) t.join();
-  }
-  if (g.local) {  // a failed call leaves the transport usable for the next one
-    std::lock_guard<std::mutex> lk(g.local->m);
-    g.local->broken = false;
-    g.local->arrived = 0;
-  }
-  if (first >= 0) {
-    if (rccl) {
-      for (auto* c : g.ctx) {
-        c->use();
-        abort_comm(*c);
-      }
-      g.broken = true;
-      try {
-        std::rethrow_exception(err[(size_t)first]);
-      } catch (const std::exception& e) {
-        g.broken_why = "member " + std::to_string(first) + ": " + e.what();
-      } catch (...) {
-        g.broken_why = "member " + std::to_string(first);
-      }
-    }
-    std::rethrow_exception(err[(size_t)first]);
-  }
-}
-// contiguous row ranges of a host CSR, one per member, balanced by entries
-std::vector<int64_t> shard_rows(const int64_t* indptr, int64_t rows, int n) {
-  std::vector<int64_t> r0((size_t)n + 1, rows);
-  r0[0] = 0;
-  const int64_t nnz = indptr[rows];
-  int64_t r = 0;
-  for (int q = 1; q < n; ++q) {
-    const int64_t target = (nnz * q + n - 1) / n;
-    while (r < rows && indptr[r] < target) ++r;
-    r0[(size_t)q] = std::max(r, r0[(size_t)q - 1]);
-  }
-  return r0;
-}
-// member i's rows [r0[i], r0[i+1]) of a host CSR uploaded to its device (indptr rebased)
-stc_dcsr* upload_rows(stc_ctx* ctx, int64_t lo, int64_t hi, int64_t cols, const int64_t* indptr,
-                      const int32_t* indices, const double* values, int dtype) {
-  std::vector<int64_t> ip((size_t)(hi - lo + 1));
-  for (int64_t r = lo; r <= hi; ++r) ip[(size_t)(r - lo)] = indptr[r] - indptr[lo];
-  stc_dcsr* d = nullptr;
-  member_ok(stc_dcsr_upload(ctx, hi - lo, cols, ip.data(), indices ? indices + indptr[lo] : nullptr,
-                            values ? values + indptr[lo] : nullptr, dtype, &d));
-  return d;
-}
-
-}  // namespace
 
 extern "C" {
 
 int stc_group_create(const int* device_ids, int n_devices, const stc_lda_config* cfg, stc_group** out) {
   return guard([&] {
     STC_REQUIRE(device_ids && cfg && out, "device_ids/cfg/out");
-    STC_REQUIRE(n_devices >= 1 && n_devices <= kMaxMembers, "1 <= n_devices <= 16");
-    int nd = 0;
-    HIP_CHECK(hipGetDeviceCount(&nd));
-    bool same = true, distinct = true;
-    for (int i = 0; i < n_devices; ++i) {
-      STC_REQUIRE(device_ids[i] >= 0 && device_ids[i] < nd, "device index out of range");
-      same &= device_ids[i] == device_ids[0];
-      for (int j = 0; j < i; ++j) distinct &= device_ids[i] != device_ids[j];
-    }
-    STC_REQUIRE(same || distinct, "device_ids: all distinct (RCCL) or all the same device (in-process)");
     auto g = std::make_unique<stc_group>();
     struct Cleanup {
       stc_group* g;
@@ -166,36 +33,8 @@ int stc_group_create(const int* device_ids, int n_devices, const stc_lda_config*
         for (auto* c : g->ctx) (void)stc_destroy(c);
       }
     } cleanup{g.get()};
-    for (int i = 0; i < n_devices; ++i) {
-      stc_ctx* c = nullptr;
-      member_ok(stc_init(device_ids[i], &c));
-      g->ctx.push_back(c);
-    }
-    // debug knob STC_GROUP_RCCL=1: a group of distinct devices — one device included — builds its RCCL
-    // communicator with ncclCommInitAll, runs the collective (vocabulary-sliced) M-step even with one member,
-    // and drives every member from its own host thread: the configs[2] drop-in path (one JVM, N GPUs,
-    // LDATraining.scala:7) exercised end to end on a one-GPU box, where no two-device communicator exists
-    const char* gr = getenv("STC_GROUP_RCCL");
-    const bool rccl1 = gr && gr[0] == '1' && distinct;
-    if (n_devices > 1 && same) {
-      g->local = std::make_unique<LocalColl>(n_devices);
-      g->transport = STC_TRANSPORT_IN_PROCESS;
-    }
-    if (n_devices > 1 || rccl1) {
-      std::vector<ncclComm_t> comms((size_t)n_devices, nullptr);
-      if (!g->local) {
-        RCCL_CHECK(ncclCommInitAll(comms.data(), n_devices, device_ids));
-        g->transport = STC_TRANSPORT_RCCL;
-      }
-      g->threaded = rccl1;
-      for (int i = 0; i < n_devices; ++i) {
-        g->ctx[(size_t)i]->comm = comms[(size_t)i];
-        g->ctx[(size_t)i]->local = g->local.get();
-        g->ctx[(size_t)i]->n_ranks = n_devices;
-        g->ctx[(size_t)i]->rank = i;
-      }
-    }
-    for (auto* c : g->ctx) c->abort_flag = &g->abort;
+    // STC_GROUP_RCCL=1 (group_common.h) also runs the collective (vocabulary-sliced) M-step with one member
+    const bool rccl1 = open_members(*g, device_ids, n_devices);
     // test knob STC_GROUP_STEP_FAULT=i[:s]: member i's s-th step (default the first) fails, after its E-step
     // and sstats and before its reduce-scatter (its peers' collectives then never complete: the RCCL
     // failure path)
@@ -223,10 +62,7 @@ int stc_group_destroy(stc_group* g) {
     if (!g) return;
     for (auto* l : g->lda) (void)stc_lda_destroy(l);
     for (auto* d : g->shard) (void)stc_dcsr_free(d);
-    for (auto* c : g->ctx) {
-      c->local = nullptr;
-      (void)stc_destroy(c);
-    }
+    close_members(*g);
     delete g;
   });
 }

@@ -16,10 +16,18 @@
 // order) and writes the partial with plain stores; k_em_fixup adds a vertex's partials in chunk order.
 // N_k and the two scalars of logLikelihood / logPrior are fixed-shape two-level reductions.  Nothing
 // depends on the grid size or on timing.
+//
+// Several devices (lda_em.h, em_group.hip): a member holds a contiguous shard of the documents with all V
+// columns.  Its row pass is the single handle's; its column pass sums the messages of its own edges into
+// N_wk' (a term without a local edge: a 0 row), the members' N_wk' are all-reduced, and N_k / inv follow on
+// every member from the same sum.  The RNG keys of kInit continue the global CSR order (pos_base), and a
+// term vertex exists iff any member has an edge of it (gdeg, all-reduced once at create).
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 
+#include "collectives.h"
+#include "lda_em.h"
 #include "stc_handles.h"
 
 namespace stc {
@@ -67,6 +75,7 @@ struct PassArgs {
   double* partial;      // n_multi×k (chunks of the others)
   double* scalar;       // kLogLik: one value per chunk
   uint64_t seed;        // kInit
+  int64_t pos_base;     // kInit: edges of the corpus before this handle's first (a group member; else 0)
   int k;
   int32_t* assign;      // kAssign: E, one topic per edge (rows only: the edge's position is its CSR position)
 };
@@ -140,7 +149,7 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
     const double cn = valid ? a.g.cnt[ed] : 0.0;
     double g[NS], sum = 0.0;
     if (MODE == kInit) {
-      const uint64_t st = doc_stream(a.seed, (uint64_t)(valid ? (a.g.pos ? a.g.pos[ed] : ed) : 0));
+      const uint64_t st = doc_stream(a.seed, (uint64_t)(valid ? (a.g.pos ? a.g.pos[ed] : ed) + a.pos_base : 0));
 #pragma unroll
       for (int i = 0; i < NS; ++i) {
         const int j = j0 + 64 * i;
@@ -204,13 +213,25 @@ __global__ void k_em_fixup(const int64_t* __restrict__ choff, const int64_t* __r
   }
 }
 
+// whether vertex v exists: it has an edge here (ptr), or, for a group member's terms, on any member (deg)
+__device__ inline bool has_vertex(const int64_t* __restrict__ ptr, const int64_t* __restrict__ deg, int64_t v) {
+  return deg ? deg[v] > 0 : ptr[v + 1] > ptr[v];
+}
+
 // rows of vertices without an edge ← 0 (an injected state keeps to the graph's vertices)
-__global__ void k_em_mask(const int64_t* __restrict__ ptr, double* __restrict__ x, int64_t n, int k) {
+__global__ void k_em_mask(const int64_t* __restrict__ ptr, const int64_t* __restrict__ deg, double* __restrict__ x,
+                          int64_t n, int k) {
   const int64_t total = n * k;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t v = t / k;
-    if (ptr[v + 1] == ptr[v]) x[t] = 0.0;
+    if (!has_vertex(ptr, deg, v)) x[t] = 0.0;
   }
+}
+
+// deg[v] = the edges of vertex v (a member's term degrees, summed over the members at create)
+__global__ void k_em_degree(const int64_t* __restrict__ ptr, int64_t n, int64_t* __restrict__ deg) {
+  const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n) deg[v] = ptr[v + 1] - ptr[v];
 }
 
 // N_k, level 1: block b sums rows [b·kSumRows, (b+1)·kSumRows) per topic — tpr lanes across the topics,
@@ -276,12 +297,13 @@ __global__ __launch_bounds__(256) void k_em_sum2(const double* __restrict__ part
 }
 
 // logPrior's per-vertex term Σ_j ln(·): terms ln φ_w[j] (inv given), documents ln θ_d[j]; 0 without an edge
-__global__ void k_em_prior(const int64_t* __restrict__ ptr, const double* __restrict__ x, int64_t n, int k, double add,
-                           const double* __restrict__ inv, double* __restrict__ out) {
+__global__ void k_em_prior(const int64_t* __restrict__ ptr, const int64_t* __restrict__ deg,
+                           const double* __restrict__ x, int64_t n, int k, double add, const double* __restrict__ inv,
+                           double* __restrict__ out) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n) return;
   double s = 0.0;
-  if (ptr[v + 1] > ptr[v]) {
+  if (has_vertex(ptr, deg, v)) {
     const double* row = x + v * k;
     if (inv) {
       for (int j = 0; j < k; ++j) s += log((row[j] + add) * inv[j]);
@@ -432,6 +454,10 @@ struct stc_em {
   DevBuf scalar;         // per-chunk / per-vertex scalars of logLikelihood / logPrior
   DevBuf result;         // 3 doubles: Σ c ln(φ·θ), Σ ln φ, Σ ln θ
   DevBuf assign;         // int32[E]: topicAssignments' output (allocated by its first call)
+  // a member of an stc_em_group (lda_em.h): D, E and the graph are its shard's
+  bool member = false;
+  int64_t pos_base = 0;  // edges in the earlier shards
+  DevBuf gdeg;           // int64[V]: every term's edges over all members (empty: the local graph is the whole one)
 };
 
 namespace stc {
@@ -494,6 +520,7 @@ void run_side(stc_em& m, bool row_side, int from, int to, uint64_t seed) {
   a.partial = m.partial.as<double>();
   a.scalar = m.scalar.as<double>();
   a.seed = seed;
+  a.pos_base = m.pos_base;
   a.k = m.k;
   a.assign = m.assign.as<int32_t>();
   launch_pass<MODE>(s, a);
@@ -517,12 +544,24 @@ void sum_to(stc_em& m, const double* x, int64_t n, double* out) {
   KERNEL_CHECK();
 }
 
-void require_idle_single(const Ctx& c) {
-  if (c.coll()) throw Error(STC_ERR_STATE, "em: the context is connected to other ranks (EM is single-device)");
+// the public entry points serve one device; a connected context's handle is driven by its stc_em_group alone
+void require_idle_single(const Ctx& c, bool as_member = false) {
+  if (c.coll() && !as_member)
+    throw Error(STC_ERR_STATE, "em: the context is connected to other ranks (EM is single-device; several devices: stc_em_group)");
+}
+void require_state(const stc_em& m) {
+  if (!m.has_state) throw Error(STC_ERR_STATE, "em: no state yet (stc_em_init_random or stc_em_set_state first)");
+}
+const int64_t* global_degrees(const stc_em& m) { return m.gdeg.p ? m.gdeg.as<int64_t>() : nullptr; }
+
+// a member's N_wk' holds the messages of its own edges: the sum over the members is the graph's
+void reduce_terms(stc_em& m, int which) {
+  if (m.member && m.ctx->coll()) coll_all_reduce(*m.ctx, m.nwk[which].p, (size_t)(m.V * m.k), ncclFloat64, m.ctx->stream);
 }
 
-stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, double topic_concentration) {
-  require_idle_single(c);
+stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, double topic_concentration,
+               bool as_member = false, int64_t pos_base = 0) {
+  require_idle_single(c, as_member);
   STC_REQUIRE(in.dtype == STC_F64, "em: the corpus values must be STC_F64");
   STC_REQUIRE(k >= 2 && k <= 1024, "em: 2 <= k <= 1024");
   STC_REQUIRE(in.rows >= 0 && in.cols > 0, "em: corpus shape");
@@ -616,7 +655,15 @@ stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, doub
                                             ceil_div(m->D, kSumElems), ceil_div(m->V, kSumElems), int64_t(1)}));
   m->scalar.reserve(8 * std::max<int64_t>({m->rows.n_chunks, m->D, m->V, int64_t(1)}));
   m->result.reserve(8 * 3);
-  HIP_CHECK(hipStreamSynchronize(s));  // the build's temporaries are freed on return
+  m->member = as_member;
+  m->pos_base = pos_base;
+  if (as_member && c.coll()) {  // which terms have a vertex is a property of the whole graph
+    m->gdeg.reserve(8 * m->V);
+    k_em_degree<<<blocks_for(m->V), 256, 0, s>>>(m->cols.ptr.as<int64_t>(), m->V, m->gdeg.as<int64_t>());
+    KERNEL_CHECK();
+    coll_all_reduce(c, m->gdeg.p, (size_t)m->V, ncclInt64, s);
+  }
+  wait_stream(c, s);  // the build's temporaries are freed on return
   return m.release();
 }
 
@@ -629,35 +676,42 @@ void destroy(stc_em* m) {
   delete m;
 }
 
-void init_random(stc_em& m, uint64_t seed) {
-  require_idle_single(*m.ctx);
+void init_random(stc_em& m, uint64_t seed, bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
   m.ctx->use();
   run_side<kInit>(m, true, 0, 0, seed);
   run_side<kInit>(m, false, 0, 0, seed);
+  reduce_terms(m, 0);
   m.cur = 0;
   refresh_totals(m, 0);
   m.has_state = true;
 }
 
-void set_state(stc_em& m, const double* doc_topics, const double* term_topics) {
-  require_idle_single(*m.ctx);
+void check_state_input(const stc_em& m, const double* doc_topics, const double* term_topics) {
   STC_REQUIRE((doc_topics || m.D == 0) && term_topics, "em: doc_topics / term_topics");
-  m.ctx->use();
-  hipStream_t s = m.ctx->stream;
   const int64_t nd = m.D * m.k, nw = m.V * m.k;
   for (int64_t i = 0; i < nd; ++i) STC_REQUIRE(doc_topics[i] >= 0.0, "em: doc_topics must be non-negative");
   for (int64_t i = 0; i < nw; ++i) STC_REQUIRE(term_topics[i] >= 0.0, "em: term_topics must be non-negative");
+}
+
+// the arrays checked by the caller; no collective: every member is given the same term_topics
+void set_state(stc_em& m, const double* doc_topics, const double* term_topics, bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
+  m.ctx->use();
+  hipStream_t s = m.ctx->stream;
+  const int64_t nd = m.D * m.k, nw = m.V * m.k;
   if (nd) HIP_CHECK(hipMemcpyAsync(m.ndk[0].p, doc_topics, 8 * nd, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(m.nwk[0].p, term_topics, 8 * nw, hipMemcpyHostToDevice, s));
   if (nd) {
-    k_em_mask<<<strided_blocks(nd), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), m.ndk[0].as<double>(), m.D, m.k);
+    k_em_mask<<<strided_blocks(nd), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), nullptr, m.ndk[0].as<double>(), m.D, m.k);
     KERNEL_CHECK();
   }
-  k_em_mask<<<strided_blocks(nw), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), m.nwk[0].as<double>(), m.V, m.k);
+  k_em_mask<<<strided_blocks(nw), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), global_degrees(m), m.nwk[0].as<double>(), m.V,
+                                               m.k);
   KERNEL_CHECK();
   m.cur = 0;
   refresh_totals(m, 0);
-  HIP_CHECK(hipStreamSynchronize(s));  // the caller's arrays are free to change on return
+  wait_stream(*m.ctx, s);  // the caller's arrays are free to change on return
   m.has_state = true;
 }
 
@@ -665,63 +719,73 @@ void get_state(stc_em& m, double* doc_topics, double* term_topics, double* total
   if (alpha_out) *alpha_out = m.alpha;
   if (eta_out) *eta_out = m.eta;
   if (!doc_topics && !term_topics && !totals) return;
-  if (!m.has_state) throw Error(STC_ERR_STATE, "em: no state yet (stc_em_init_random or stc_em_set_state first)");
+  require_state(m);
   m.ctx->use();
   hipStream_t s = m.ctx->stream;
   if (doc_topics && m.D) HIP_CHECK(hipMemcpyAsync(doc_topics, m.ndk[m.cur].p, 8 * m.D * m.k, hipMemcpyDeviceToHost, s));
   if (term_topics) HIP_CHECK(hipMemcpyAsync(term_topics, m.nwk[m.cur].p, 8 * m.V * m.k, hipMemcpyDeviceToHost, s));
   if (totals) HIP_CHECK(hipMemcpyAsync(totals, m.nk.p, 8 * m.k, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
+  wait_stream(*m.ctx, s);
 }
 
-void next(stc_em& m, int32_t n_iterations) {
-  require_idle_single(*m.ctx);
+void next(stc_em& m, int32_t n_iterations, bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
   STC_REQUIRE(n_iterations >= 0, "em: n_iterations >= 0");
-  if (!m.has_state) throw Error(STC_ERR_STATE, "em: no state yet (stc_em_init_random or stc_em_set_state first)");
+  require_state(m);
   m.ctx->use();
   for (int32_t it = 0; it < n_iterations; ++it) {
     const int from = m.cur, to = 1 - m.cur;
     run_side<kUpdate>(m, true, from, to, 0);   // N_dk' over rows, gathering N_wk
     run_side<kUpdate>(m, false, from, to, 0);  // N_wk' over columns, gathering N_dk
+    reduce_terms(m, to);                       // a group member: + the other members' edges
     refresh_totals(m, to);                     // N_k' and 1 / (N_k' + V(η−1)) for the next reads
     m.cur = to;
   }
 }
 
-void log_likelihood(stc_em& m, double* ll_out, double* prior_out) {
-  require_idle_single(*m.ctx);
-  if (!m.has_state) throw Error(STC_ERR_STATE, "em: no state yet (stc_em_init_random or stc_em_set_state first)");
+// h[0] Σ c ln(φ·θ) over the edges, h[1] Σ ln φ over the term vertices, h[2] Σ ln θ over the document vertices
+void log_likelihood_parts(stc_em& m, bool want_ll, bool want_prior, double h[3], bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
+  require_state(m);
   m.ctx->use();
   hipStream_t s = m.ctx->stream;
   double* res = m.result.as<double>();
-  double h[3] = {0, 0, 0};
-  if (ll_out) {
+  h[0] = h[1] = h[2] = 0.0;
+  if (want_ll) {
     run_side<kLogLik>(m, true, m.cur, m.cur, 0);
     sum_to(m, m.scalar.as<double>(), m.rows.n_chunks, res);
   }
-  if (prior_out) {
-    k_em_prior<<<blocks_for(m.V), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), m.nwk[m.cur].as<double>(), m.V, m.k, m.eta - 1.0,
-                                               m.inv.as<double>(), m.scalar.as<double>());
+  if (want_prior) {
+    k_em_prior<<<blocks_for(m.V), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), global_degrees(m), m.nwk[m.cur].as<double>(), m.V,
+                                               m.k, m.eta - 1.0, m.inv.as<double>(), m.scalar.as<double>());
     KERNEL_CHECK();
     sum_to(m, m.scalar.as<double>(), m.V, res + 1);
     if (m.D > 0) {
-      k_em_prior<<<blocks_for(m.D), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), m.ndk[m.cur].as<double>(), m.D, m.k,
+      k_em_prior<<<blocks_for(m.D), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), nullptr, m.ndk[m.cur].as<double>(), m.D, m.k,
                                                  m.alpha - 1.0, nullptr, m.scalar.as<double>());
       KERNEL_CHECK();
     }
     sum_to(m, m.scalar.as<double>(), m.D, res + 2);
   }
-  if (ll_out || prior_out) {
-    HIP_CHECK(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+  if (want_ll || want_prior) {
+    double r[3] = {0, 0, 0};
+    HIP_CHECK(hipMemcpyAsync(r, res, sizeof r, hipMemcpyDeviceToHost, s));
+    wait_stream(*m.ctx, s);
+    if (want_ll) h[0] = r[0];
+    if (want_prior) h[1] = r[1], h[2] = r[2];
   }
+}
+
+void log_likelihood(stc_em& m, double* ll_out, double* prior_out) {
+  double h[3];
+  log_likelihood_parts(m, ll_out != nullptr, prior_out != nullptr, h);
   if (ll_out) *ll_out = h[0];
   if (prior_out) *prior_out = (m.eta - 1.0) * h[1] + (m.alpha - 1.0) * h[2];
 }
 
-void topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out) {
-  require_idle_single(*m.ctx);
-  if (!m.has_state) throw Error(STC_ERR_STATE, "em: no state yet (stc_em_init_random or stc_em_set_state first)");
+void topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out, bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
+  require_state(m);
   m.ctx->use();
   hipStream_t s = m.ctx->stream;
   m.assign.reserve(4 * std::max<int64_t>(m.E, 1));
@@ -730,7 +794,7 @@ void topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32
   if (indptr_out) HIP_CHECK(hipMemcpyAsync(indptr_out, m.rows.ptr.p, 8 * (m.D + 1), hipMemcpyDeviceToHost, s));
   if (terms_out && m.E) HIP_CHECK(hipMemcpyAsync(terms_out, m.rows.idx.p, 4 * m.E, hipMemcpyDeviceToHost, s));
   if (topics_out && m.E) HIP_CHECK(hipMemcpyAsync(topics_out, m.assign.p, 4 * m.E, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
+  wait_stream(*m.ctx, s);
 }
 
 void shape(const stc_em& m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges) {
@@ -741,6 +805,32 @@ void shape(const stc_em& m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t
 }
 
 }  // namespace
+
+// ---- the member side of an stc_em_group (lda_em.h) --------------------------------------------------
+stc_em* member_create(Ctx& c, const DCsr& shard, int32_t k, double doc_concentration, double topic_concentration,
+                      int64_t pos_base) {
+  return create(c, shard, k, doc_concentration, topic_concentration, true, pos_base);
+}
+void member_init_random(stc_em& m, uint64_t seed) { init_random(m, seed, true); }
+void member_set_state(stc_em& m, const double* doc_topics, const double* term_topics) {
+  set_state(m, doc_topics, term_topics, true);
+}
+void member_next(stc_em& m, int32_t n_iterations) { next(m, n_iterations, true); }
+void member_log_likelihood(stc_em& m, double* ll, double* term_prior, double* doc_prior) {
+  double h[3];
+  log_likelihood_parts(m, ll != nullptr, term_prior || doc_prior, h, true);
+  if (ll) *ll = h[0];
+  if (term_prior) *term_prior = h[1];
+  if (doc_prior) *doc_prior = h[2];
+}
+void member_topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out) {
+  topic_assignments(m, indptr_out, terms_out, topics_out, true);
+}
+void member_wait(stc_em& m) {
+  m.ctx->use();
+  wait_stream(*m.ctx, m.ctx->stream);
+}
+
 }  // namespace em
 }  // namespace stc
 
@@ -777,6 +867,8 @@ int stc_em_init_random(stc_em* m, uint64_t seed) {
 int stc_em_set_state(stc_em* m, const double* doc_topics, const double* term_topics) {
   return guard([&] {
     STC_REQUIRE(m, "em");
+    require_idle_single(*m->ctx);
+    em::check_state_input(*m, doc_topics, term_topics);
     em::set_state(*m, doc_topics, term_topics);
   });
 }

@@ -7,8 +7,9 @@ from ._lib import (STC_ERR_HIP, STC_ERR_INVALID_ARG, STC_ERR_OOM, STC_ERR_RCCL, 
                    STC_HASH_SPARK24, STC_HASH_STANDARD, STC_LAYOUT_KV, STC_LAYOUT_VK, StcError, StcIllegalArgument,
                    load)
 from . import io
-from .clustering import (LDA, ML_LDA_DEFAULT_SEED, DistributedLDAModel, EmHandle, EMLDAOptimizer, LdaGroup, LdaHandle,
-                         LDAModel, MllibLDA, OnlineLDAOptimizer, em_concentrations, reference_mini_batch_fraction)
+from .clustering import (LDA, ML_LDA_DEFAULT_SEED, DistributedLDAModel, EmGroup, EmHandle, EMLDAOptimizer, LdaGroup,
+                         LdaHandle, LDAModel, MllibLDA, OnlineLDAOptimizer, em_concentrations,
+                         reference_mini_batch_fraction)
 from .core import Context, CsrMatrix, DeviceCsr
 from .count_vectorizer import CountVectorizer, CountVectorizerModel
 from .feature import IDF, DeviceTokens, HashingTF, IDFModel, Tokenizer, encode_texts, encode_tokens
@@ -16,7 +17,7 @@ from .text_prep import DEFAULT_STRIP_CHARS, PorterStemmer, TextPreprocessor
 
 __all__ = [
     "Context", "CsrMatrix", "DeviceCsr", "CountVectorizer", "CountVectorizerModel", "HashingTF", "IDF", "IDFModel", "Tokenizer", "DeviceTokens", "TextPreprocessor", "PorterStemmer", "DEFAULT_STRIP_CHARS", "encode_texts", "encode_tokens", "LDA",
-    "LDAModel", "DistributedLDAModel", "LdaGroup", "LdaHandle", "EmHandle", "io", "MllibLDA", "OnlineLDAOptimizer",
+    "LDAModel", "DistributedLDAModel", "LdaGroup", "LdaHandle", "EmHandle", "EmGroup", "io", "MllibLDA", "OnlineLDAOptimizer",
     "EMLDAOptimizer", "em_concentrations", "ML_LDA_DEFAULT_SEED", "reference_mini_batch_fraction", "StcError", "StcIllegalArgument", "load", "STC_F32", "STC_F64", "STC_MIXED",
     "STC_HASH_STANDARD", "STC_HASH_SPARK24", "STC_LAYOUT_VK", "STC_LAYOUT_KV", "STC_ERR_INVALID_ARG", "STC_ERR_HIP",
     "STC_ERR_RCCL", "STC_ERR_OOM", "STC_ERR_STATE",

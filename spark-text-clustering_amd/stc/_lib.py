@@ -168,6 +168,19 @@ SIGNATURES = {
     "stc_group_describe": (_int, [_p, _i32, _pi32, _pdbl]),
     "stc_group_bound": (_int, [_p, _i64, _i64, _pi64, _pi32, _pdbl, _u64, _i64, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
     "stc_group_topic_distribution": (_int, [_p, _i64, _i64, _pi64, _pi32, _pdbl, _u64, _i64, _pdbl, _pdbl]),
+    "stc_em_group_create": (_int, [_pi32, _int, _i64, _i64, _pi64, _pi32, _pdbl, _i32, _dbl, _dbl, C.POINTER(_p)]),
+    "stc_em_group_destroy": (_int, [_p]),
+    "stc_em_group_size": (_int, [_p, _pi32]),
+    "stc_em_group_transport": (_int, [_p, _pi32]),
+    "stc_em_group_shape": (_int, [_p, _pi32, _pi64, _pi64, _pi64]),
+    "stc_em_group_member": (_int, [_p, _int, C.POINTER(_p), _pi64]),
+    "stc_em_group_init_random": (_int, [_p, _u64]),
+    "stc_em_group_set_state": (_int, [_p, _pdbl, _pdbl]),
+    "stc_em_group_get_state": (_int, [_p, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
+    "stc_em_group_next": (_int, [_p, _i32]),
+    "stc_em_group_synchronize": (_int, [_p]),
+    "stc_em_group_log_likelihood": (_int, [_p, _pdbl, _pdbl]),
+    "stc_em_group_topic_assignments": (_int, [_p, _pi64, _pi32, _pi32]),
 }
 
 

@@ -11,7 +11,9 @@
 * ``EMLDAOptimizer`` + ``MllibLDA.setOptimizer("em")`` is the reference's default branch (Params.scala:9,
   LDAClustering.scala:40-41): ``run`` trains on the GPU through an ``EmHandle`` (stc_em_*: the corpus as a
   bipartite graph, N_dk / N_wk / N_k in fp64) and returns a ``DistributedLDAModel`` with logLikelihood,
-  logPrior, topicDistributions, topTopicsPerDocument, topDocumentsPerTopic and save.
+  logPrior, topicDistributions, topTopicsPerDocument, topDocumentsPerTopic and save.  With ``devices`` set
+  (``MllibLDA(devices=[0, 1])`` / ``setDevices``) the same run goes through an ``EmGroup`` (stc_em_group_*: the
+  documents sharded over the devices, N_wk all-reduced once per iteration).
 
 The ml estimator ``LDA`` stays online-only (the reference selects EM on the mllib class); an optimizer
 other than "em" / "online" raises as in LDAClustering.scala:44-45.
@@ -431,6 +433,109 @@ class EmHandle:
             pass
 
 
+class EmGroup:
+    """Owns one stc_em_group: the EM optimizer over several devices from ONE process.  The host ``corpus`` is
+    sharded by the library (contiguous document ranges balanced by entries; document ids stay global); N_dk is
+    kept by the member that owns the document, N_wk and N_k are replicated and all-reduced once per iteration.
+    ``devices`` repeating one device runs that decomposition on the one device.  ``EmHandle``'s methods and
+    attributes, over the whole corpus."""
+
+    def __init__(self, devices, corpus: CsrMatrix, k, doc_concentration=-1.0, topic_concentration=-1.0):
+        self.lib = L.load()
+        self.handle = None
+        devs = np.ascontiguousarray(np.asarray(devices, np.int32))
+        ip, ix, v = L.as_i64(corpus.indptr), np.ascontiguousarray(corpus.indices, np.int32), L.as_f64(corpus.values)
+        h = C.c_void_p()
+        L.check(self.lib.stc_em_group_create(L.ptr(devs, C.c_int32), devs.size, corpus.num_rows, corpus.num_cols,
+                                             L.ptr(ip, C.c_int64), L.ptr(ix, C.c_int32), L.ptr(v, C.c_double), int(k),
+                                             float(doc_concentration), float(topic_concentration), C.byref(h)))
+        self.handle = h
+        self.devices = devs.tolist()
+        kk, d, vv, e = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        L.check(self.lib.stc_em_group_shape(h, C.byref(kk), C.byref(d), C.byref(vv), C.byref(e)))
+        self.k, self.num_docs, self.vocab_size, self.num_edges = kk.value, d.value, vv.value, e.value
+
+    def members(self):
+        """[(member stc_em handle, its first corpus row)], for reading only: stc_em_shape, stc_em_get_state"""
+        out = []
+        for i in range(len(self.devices)):
+            h, r0 = C.c_void_p(), C.c_int64()
+            L.check(self.lib.stc_em_group_member(self.handle, i, C.byref(h), C.byref(r0)))
+            out.append((h, r0.value))
+        return out
+
+    def transport(self):
+        """ "none" (one member), "in-process" (one device repeated) or "rccl" """
+        t = C.c_int32()
+        L.check(self.lib.stc_em_group_transport(self.handle, C.byref(t)))
+        return {L.STC_TRANSPORT_NONE: "none", L.STC_TRANSPORT_IN_PROCESS: "in-process",
+                L.STC_TRANSPORT_RCCL: "rccl"}[t.value]
+
+    def synchronize(self):
+        """waits for every member's queued iterations"""
+        L.check(self.lib.stc_em_group_synchronize(self.handle))
+
+    def init_random(self, seed):
+        L.check(self.lib.stc_em_group_init_random(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def set_state(self, doc_topics, term_topics):
+        dt, tt = L.as_f64(doc_topics), L.as_f64(term_topics)
+        if dt.shape != (self.num_docs, self.k) or tt.shape != (self.vocab_size, self.k):
+            raise ValueError(f"state shapes {dt.shape}, {tt.shape}: expected ({self.num_docs}, {self.k}) and "
+                             f"({self.vocab_size}, {self.k})")
+        L.check(self.lib.stc_em_group_set_state(self.handle, L.ptr(dt, C.c_double), L.ptr(tt, C.c_double)))
+
+    def state(self):
+        """(N_dk D×k gathered from the members, N_wk V×k and N_k k of member 0); waits for queued iterations"""
+        dt = np.zeros((self.num_docs, self.k), np.float64)
+        tt = np.zeros((self.vocab_size, self.k), np.float64)
+        nk = np.zeros(self.k, np.float64)
+        L.check(self.lib.stc_em_group_get_state(self.handle, L.ptr(dt, C.c_double), L.ptr(tt, C.c_double),
+                                                L.ptr(nk, C.c_double), None, None))
+        return dt, tt, nk
+
+    def concentrations(self):
+        """the resolved (docConcentration α, topicConcentration η)"""
+        a, e = C.c_double(), C.c_double()
+        L.check(self.lib.stc_em_group_get_state(self.handle, None, None, None, C.byref(a), C.byref(e)))
+        return a.value, e.value
+
+    def next(self, n_iterations=1):
+        L.check(self.lib.stc_em_group_next(self.handle, int(n_iterations)))
+
+    def log_likelihood(self):
+        """(logLikelihood, logPrior) of the current state"""
+        ll, lp = C.c_double(), C.c_double()
+        L.check(self.lib.stc_em_group_log_likelihood(self.handle, C.byref(ll), C.byref(lp)))
+        return ll.value, lp.value
+
+    def topic_assignments(self):
+        """(indptr int64[D+1], terms int32[E], topics int32[E]) in the whole corpus's filtered CSR order"""
+        indptr = np.zeros(self.num_docs + 1, np.int64)
+        terms = np.zeros(self.num_edges, np.int32)
+        topics = np.zeros(self.num_edges, np.int32)
+        L.check(self.lib.stc_em_group_topic_assignments(self.handle, L.ptr(indptr, C.c_int64), L.ptr(terms, C.c_int32),
+                                                        L.ptr(topics, C.c_int32)))
+        return indptr, terms, topics
+
+    def close(self):
+        if self.handle:
+            self.lib.stc_em_group_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _as_device(ctx, data, dtype):
     if isinstance(data, DeviceCsr):
         return data, False
@@ -532,7 +637,7 @@ class DistributedLDAModel:
     (LDAClustering.scala:75) and ``topicAssignments`` run on the GPU; a loaded model builds its ``EmHandle`` from the stored edges
     and state on first use, so the reference's own saved models can be scored."""
 
-    def __init__(self, data, em: "EmHandle | None" = None):
+    def __init__(self, data, em: "EmHandle | EmGroup | None" = None):
         self._d = data
         self.k, self.vocabSize = data["k"], data["vocab_size"]
         self.docConcentration = data["alpha"]
@@ -544,8 +649,9 @@ class DistributedLDAModel:
         self._em_rows_are_ids = em is not None  # the trainer's graph: row = document id; a rebuilt one: its rank
 
     @staticmethod
-    def _from_em(em: "EmHandle", corpus: CsrMatrix, iteration_times, gamma_shape=100.0) -> "DistributedLDAModel":
-        """the model of a trained EmHandle over the host copy of its corpus (vertex id = row index)"""
+    def _from_em(em: "EmHandle | EmGroup", corpus: CsrMatrix, iteration_times,
+                 gamma_shape=100.0) -> "DistributedLDAModel":
+        """the model of a trained EmHandle or EmGroup over the host copy of its corpus (vertex id = row index)"""
         ndk, nwk, nk = em.state()
         alpha, eta = em.concentrations()
         keep = corpus.values != 0.0
@@ -557,7 +663,7 @@ class DistributedLDAModel:
             "alpha": np.full(em.k, alpha), "eta": eta, "gamma_shape": float(gamma_shape),
             "iteration_times": np.asarray(iteration_times, np.float64), "k": em.k, "vocab_size": em.vocab_size}, em=em)
 
-    def _em_handle(self, ctx: Context | None = None) -> "EmHandle":
+    def _em_handle(self, ctx: Context | None = None) -> "EmHandle | EmGroup":
         """the GPU graph of this model: the trainer's, or one built from the stored edges and state"""
         if self._em is None:
             d = self._d
@@ -820,15 +926,23 @@ def em_concentrations(k, docConcentration=-1.0, topicConcentration=-1.0):
 
 class MllibLDA:
     """mllib.clustering.LDA as driven at LDAClustering.scala:37-61: the optimizer switch of :40-46 takes
-    ``"em"`` / ``EMLDAOptimizer`` (the reference's default) or ``"online"`` / ``OnlineLDAOptimizer``."""
+    ``"em"`` / ``EMLDAOptimizer`` (the reference's default) or ``"online"`` / ``OnlineLDAOptimizer``.
+    ``devices`` (or ``setDevices``): the EM optimizer trains over those devices through an ``EmGroup``."""
 
-    def __init__(self, ctx: Context | None = None):
+    def __init__(self, ctx: Context | None = None, devices=None):
         self.k, self.maxIterations, self.docConcentration, self.topicConcentration = 10, 20, -1.0, -1.0
         self.seed = _java_string_hash("org.apache.spark.mllib.clustering.LDA")
         self.optimizer = OnlineLDAOptimizer()
         self.checkpointInterval = 10
         self.dtype = "f64"
         self._ctx = ctx
+        self.devices = None if devices is None else [int(d) for d in devices]
+
+    def setDevices(self, devices):
+        """the devices the EM optimizer trains over (one repeated: the same decomposition on that device);
+        None: the context's device alone"""
+        self.devices = None if devices is None else [int(d) for d in devices]
+        return self
 
     def setOptimizer(self, opt):
         if isinstance(opt, str):
@@ -871,6 +985,18 @@ class MllibLDA:
         import time
 
         alpha, eta = em_concentrations(self.k, self.docConcentration, self.topicConcentration)
+        if self.devices is not None:
+            host = corpus.download() if isinstance(corpus, DeviceCsr) else corpus
+            em = EmGroup(self.devices, host, self.k, alpha, eta)
+            em.init_random(self.seed)
+            em.synchronize()
+            self.iterationTimes = []
+            for _ in range(self.maxIterations):
+                t0 = time.perf_counter()
+                em.next(1)
+                em.synchronize()
+                self.iterationTimes.append(time.perf_counter() - t0)
+            return DistributedLDAModel._from_em(em, host, self.iterationTimes)
         ctx = self._ctx or Context.get()
         if isinstance(corpus, DeviceCsr):
             dev, host = corpus, corpus.download()

@@ -20,7 +20,14 @@ copied out) is timed in the same run under the same discipline, from the state t
 term index, one gathered k-row and the 4 B result per edge: E·(8 + 8k).  The row pass it is to be read
 against is one kernel of the iteration; its time comes from a kernel trace of this tool's run.
 
+--devices 0,0 or 0,1,… runs the same cases through an EmGroup (stc_em_group: documents sharded over the members,
+one all-reduce of N_wk' per iteration) and reports the same lines, with "devices" and "transport" added.  A
+repeated device shows the decomposition's overhead on one GPU only: the in-process transport synchronises the
+host inside every all-reduce, so it says nothing about scaling.  STC_GROUP_RCCL=1 with --devices 0 is the
+one-member group over a real RCCL communicator.
+
     python tools/bench_em.py [--case golden|zipf|all] [--iters 20] [--warmup 3] [--repeats 5] [--workers N]
+                             [--devices 0,0]
 """
 import argparse
 import json
@@ -36,7 +43,18 @@ sys.path[:0] = [os.path.join(ROOT, "spark-text-clustering_amd"), ROOT]
 GOLDEN_MODEL = os.path.join(ROOT, "tests", "golden", "LdaModel_EN_1591049082850")
 
 
-def golden_case(stc, ctx):
+def make_handle(stc, ctx, devices, corpus, k, alpha=-1.0, eta=-1.0):
+    """(handle, synchronize): an EmHandle on ctx, or an EmGroup over `devices`"""
+    if devices:
+        g = stc.EmGroup(devices, corpus, k, alpha, eta)
+        return g, g.synchronize
+    dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
+    h = stc.EmHandle(ctx, dev, k, alpha, eta)
+    dev.free()
+    return h, ctx.synchronize
+
+
+def golden_case(stc, ctx, devices):
     m = stc.io.load_distributed(GOLDEN_MODEL)
     src, term, cnt = m["edges"]
     row = np.searchsorted(m["doc_ids"], src)
@@ -44,59 +62,59 @@ def golden_case(stc, ctx):
     indptr = np.zeros(m["doc_ids"].size + 1, np.int64)
     np.cumsum(np.bincount(row, minlength=m["doc_ids"].size), out=indptr[1:])
     corpus = stc.CsrMatrix(indptr, term[order], cnt[order], m["vocab_size"])
-    dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
-    h = stc.EmHandle(ctx, dev, m["k"], float(m["alpha"][0]), m["eta"])
-    dev.free()
+    h, sync = make_handle(stc, ctx, devices, corpus, m["k"], float(m["alpha"][0]), m["eta"])
     h.set_state(m["doc_topics"], m["topics"])
     ref = float(np.median(m["iteration_times"]))
-    return h, {"case": "golden", "reference_s_per_iteration": ref,
+    return h, sync, {"case": "golden", "reference_s_per_iteration": ref,
                "reference_note": "median of the saved model's 50 iterationTimes; unknown PC, Spark local[*]"}
 
 
-def zipf_case(stc, ctx, docs, tokens, vocab, k, workers):
+def zipf_case(stc, ctx, devices, docs, tokens, vocab, k, workers):
     from stc import synth
 
     corpus = synth.zipf_corpus(docs, tokens, vocab, workers=workers)
-    dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
-    h = stc.EmHandle(ctx, dev, k)
-    dev.free()
+    h, sync = make_handle(stc, ctx, devices, corpus, k)
     h.init_random(1)
-    return h, {"case": "zipf", "docs": docs, "tokens_per_doc": tokens}
+    return h, sync, {"case": "zipf", "docs": docs, "tokens_per_doc": tokens}
 
 
-def assign_pass_ms(ctx, h, iters, warmup, repeats):
+def assign_pass_ms(ctx, h, sync, iters, warmup, repeats):
     """ms per topicAssignments pass without the copy-out, per repeat"""
     from stc import _lib as L
 
+    fn = ctx.lib.stc_em_group_topic_assignments if hasattr(h, "members") else ctx.lib.stc_em_topic_assignments
+
     def enqueue(n):
         for _ in range(n):
-            L.check(ctx.lib.stc_em_topic_assignments(h.handle, None, None, None))
+            L.check(fn(h.handle, None, None, None))
 
     enqueue(warmup)
-    ctx.synchronize()
+    sync()
     ms = []
     for _ in range(repeats):
         t0 = time.perf_counter()
         enqueue(iters)
-        ctx.synchronize()
+        sync()
         ms.append((time.perf_counter() - t0) * 1e3 / iters)
     return ms
 
 
-def measure(ctx, h, info, iters, warmup, repeats):
+def measure(ctx, h, sync, info, iters, warmup, repeats):
     h.next(warmup)
-    ctx.synchronize()
+    sync()
     ms = []
     for _ in range(repeats):
         t0 = time.perf_counter()
         h.next(iters)
-        ctx.synchronize()
+        sync()  # a group: every member, once per timed batch
         ms.append((time.perf_counter() - t0) * 1e3 / iters)
     med = float(np.median(ms))
     E, k = h.num_edges, h.k
     algo_bytes = 2.0 * E * (12 + 8 * k)
     ll, lp = h.log_likelihood()
-    ams = assign_pass_ms(ctx, h, iters, warmup, repeats)
+    ams = assign_pass_ms(ctx, h, sync, iters, warmup, repeats)
+    if hasattr(h, "members"):
+        info = dict(info, devices=h.devices, transport=h.transport())
     amed = float(np.median(ams))
     out = dict(info, n_docs=h.num_docs, vocab=h.vocab_size, k=k, edges=E, iters=iters, warmup=warmup, repeats=repeats,
                ms_per_iteration=med, ms_per_iteration_min=float(min(ms)), ms_per_iteration_max=float(max(ms)),
@@ -121,13 +139,17 @@ def main():
     p.add_argument("--k", type=int, default=100)
     p.add_argument("--workers", type=int, default=min(16, os.cpu_count() or 1),
                    help="corpus-generation processes of the zipf case (1 under a profiler: nothing is forked)")
+    p.add_argument("--devices", default="",
+                   help="comma-separated device ids of an EmGroup (0,0: two members on device 0); empty: one EmHandle")
     a = p.parse_args()
     import stc
 
+    devices = [int(d) for d in a.devices.split(",") if d.strip()]
     ctx = stc.Context.get(0)
     for case in (("golden", "zipf") if a.case == "all" else (a.case,)):
-        h, info = golden_case(stc, ctx) if case == "golden" else zipf_case(stc, ctx, a.docs, a.tokens, a.vocab, a.k, a.workers)
-        print(json.dumps(measure(ctx, h, info, a.iters, a.warmup, a.repeats)), flush=True)
+        h, sync, info = (golden_case(stc, ctx, devices) if case == "golden" else
+                         zipf_case(stc, ctx, devices, a.docs, a.tokens, a.vocab, a.k, a.workers))
+        print(json.dumps(measure(ctx, h, sync, info, a.iters, a.warmup, a.repeats)), flush=True)
         h.close()
 
 
