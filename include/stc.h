@@ -403,7 +403,7 @@ int stc_lda_kernel_counts(stc_lda* lda, int64_t out[12]);
 /* ---- EM LDA ([U] EMLDAOptimizer → DistributedLDAModel) ------------------------------------
  * The corpus is a bipartite graph: every CSR entry (document d, term w, value c != 0) is an edge; entries
  * whose value is exactly 0 are not edges, and a document or term without an edge has no vertex (its row of
- * the state is 0).  State, fp64: doc_topics N_dk (D×k), term_topics N_wk (V×k, the model's unnormalised
+ * the state is 0).  State, fp64 (stored as fp32 by stc_em_create_as, below): doc_topics N_dk (D×k), term_topics N_wk (V×k, the model's unnormalised
  * topicsMatrix), totals N_k = Σ_w N_wk.  One iteration: along every edge the message c·γ with
  *   γ_j ∝ (N_wk[w][j] + η−1)(N_dk[d][j] + α−1) / (N_k[j] + V(η−1)),  Σ_j γ_j = 1,
  * all reads from the old state; a vertex's new counts are the sum of the messages of its edges.
@@ -541,6 +541,31 @@ int stc_em_group_synchronize(stc_em_group* g);
 int stc_em_group_log_likelihood(stc_em_group* g, double* log_likelihood_out, double* log_prior_out);
 /* as stc_em_topic_assignments, in the whole corpus's filtered CSR order: indptr_out int64[D+1] */
 int stc_em_group_topic_assignments(stc_em_group* g, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out);
+
+/* ---- EM LDA, fp32 state storage -----------------------------------------------------------
+ * state_dtype STC_F64 is stc_em_create / stc_em_group_create (bitwise); STC_F32 stores N_dk and N_wk as fp32;
+ * anything else: STC_ERR_INVALID_ARG.  The contract of an STC_F32 handle: it runs exactly the fp64 handle's
+ * iteration on the values it stores, and rounds each new N_dk / N_wk element to the nearest fp32 once, when it
+ * is stored.  Everything else stays fp64, in the fp64 handle's order: the edge counts, α, η, N_k (the fixed-shape
+ * column sum of the stored, rounded N_wk), γ, every accumulator and partial sum, logLikelihood, logPrior and the
+ * argmax of topicAssignments.  So on one device every result of an STC_F32 handle is bitwise that of an STC_F64
+ * handle given the same fp32-valued state, rounded.  Elements below fp32's normal range (2^-126) are unpinned.
+ * The corpus stays STC_F64 (counts and TF·IDF weights are not rounded; an STC_F32 corpus is still refused).
+ * stc_em_set_state takes doubles and stores them rounded to nearest, after the vertex mask; stc_em_get_state
+ * returns the stored values widened to doubles, which is exact.  init_random rounds its sums the same way.
+ * A group of STC_F32 members: each member's partial N_wk' row is rounded when stored and the members' partials
+ * are added in fp32 (the all-reduce carries fp32: half the bytes; the in-process transport adds in member
+ * order); N_dk' is the single handle's.
+ * (Declared as a block of their own; the arguments before state_dtype are stc_em_create's and
+ * stc_em_group_create's.) */
+  int stc_em_create_as(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
+                       double topic_concentration, int state_dtype /* STC_F64 | STC_F32 */, stc_em** out);
+  /* STC_F64 or STC_F32; serves a member of a group too */
+  int stc_em_state_dtype(const stc_em* em, int* dtype_out);
+  int stc_em_group_create_as(const int* device_ids, int n_devices, int64_t n_rows, int64_t n_cols,
+                             const int64_t* indptr, const int32_t* indices, const double* values, int32_t k,
+                             double doc_concentration, double topic_concentration, int state_dtype,
+                             stc_em_group** out);
 
 #ifdef __cplusplus
 }

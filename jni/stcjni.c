@@ -622,6 +622,20 @@ JNIEXPORT jlong JNICALL FN(emCreate)(JNIEnv* env, jclass c, jlong ctx, jlong dcs
   return (jlong)(intptr_t)out;
 }
 
+/* stateDtype: STC_F64 (emCreate) or STC_F32 (N_dk / N_wk stored as fp32) */
+JNIEXPORT jlong JNICALL FN(emCreateAs)(JNIEnv* env, jclass c, jlong ctx, jlong dcsr, jint k, jdouble alpha, jdouble eta,
+                                       jint state_dtype) {
+  stc_em* out = NULL;
+  if (check(env, stc_em_create_as(CTX(ctx), CSR(dcsr), k, alpha, eta, state_dtype, &out))) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT jint JNICALL FN(emStateDtype)(JNIEnv* env, jclass c, jlong em) {
+  int t = 0;
+  check(env, stc_em_state_dtype(EM(em), &t));
+  return t;
+}
+
 JNIEXPORT void JNICALL FN(emDestroy)(JNIEnv* env, jclass c, jlong em) { check(env, stc_em_destroy(EM(em))); }
 
 /* {k, nDocs, vocabSize, nEdges} */
@@ -1135,6 +1149,29 @@ JNIEXPORT jlong JNICALL FN(emGroupCreate)(JNIEnv* env, jclass c, jintArray devic
   stc_em_group* out = NULL;
   int st = stc_em_group_create((const int*)dv, (int)LEN(devices), rows, cols, (const int64_t*)ip, (const int32_t*)ix, vs,
                                k, alpha, eta, &out);
+  UNPIN(Double, values, vs, JNI_ABORT);
+  UNPIN(Int, indices, ix, JNI_ABORT);
+  UNPIN(Long, indptr, ip, JNI_ABORT);
+  UNPIN(Int, devices, dv, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT jlong JNICALL FN(emGroupCreateAs)(JNIEnv* env, jclass c, jintArray devices, jlong rows, jlong cols,
+                                            jlongArray indptr, jintArray indices, jdoubleArray values, jint k,
+                                            jdouble alpha, jdouble eta, jint state_dtype) {
+  if (!devices || LEN(devices) < 1) {
+    throw_iae(env, "emGroupCreateAs: at least one device id");
+    return 0;
+  }
+  if (csr_args(env, rows, indptr, indices, values, "emGroupCreateAs")) return 0;
+  jint* dv = PIN(jint, Int, devices);
+  jlong* ip = PIN(jlong, Long, indptr);
+  jint* ix = PIN(jint, Int, indices);
+  jdouble* vs = PIN(jdouble, Double, values);
+  stc_em_group* out = NULL;
+  int st = stc_em_group_create_as((const int*)dv, (int)LEN(devices), rows, cols, (const int64_t*)ip, (const int32_t*)ix,
+                                  vs, k, alpha, eta, state_dtype, &out);
   UNPIN(Double, values, vs, JNI_ABORT);
   UNPIN(Int, indices, ix, JNI_ABORT);
   UNPIN(Long, indptr, ip, JNI_ABORT);

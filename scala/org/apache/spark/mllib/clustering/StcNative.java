@@ -108,6 +108,11 @@ public final class StcNative {
 
   // ---- EM LDA (stc_em_*: EMLDAOptimizer / DistributedLDAModel; docConcentration / topicConcentration −1 = auto)
   public static native long emCreate(long ctx, long dcsr, int k, double docConcentration, double topicConcentration);
+  /** stateDtype: STC_F64 = 1 (emCreate) or STC_F32 = 0: N_dk / N_wk stored as fp32, all arithmetic in fp64 */
+  public static native long emCreateAs(long ctx, long dcsr, int k, double docConcentration, double topicConcentration,
+                                       int stateDtype);
+  /** STC_F64 = 1 or STC_F32 = 0; serves a group member's handle too */
+  public static native int emStateDtype(long em);
   public static native void emDestroy(long em);
   /** {k, nDocs, vocabSize, nEdges} of the handle */
   public static native long[] emShape(long em);
@@ -214,6 +219,9 @@ public final class StcNative {
   public static native long emGroupCreate(int[] deviceIds, long rows, long cols, long[] indptr, int[] indices,
                                           double[] values, int k, double docConcentration,
                                           double topicConcentration);
+  public static native long emGroupCreateAs(int[] deviceIds, long rows, long cols, long[] indptr, int[] indices,
+                                            double[] values, int k, double docConcentration,
+                                            double topicConcentration, int stateDtype);
   public static native void emGroupDestroy(long emGroup);
   public static native int emGroupSize(long emGroup);
   public static native int emGroupTransport(long emGroup);

@@ -39,12 +39,13 @@ void destroy(stc_em_group* g) {
 
 extern "C" {
 
-int stc_em_group_create(const int* device_ids, int n_devices, int64_t n_rows, int64_t n_cols, const int64_t* indptr,
-                        const int32_t* indices, const double* values, int32_t k, double doc_concentration,
-                        double topic_concentration, stc_em_group** out) {
+int stc_em_group_create_as(const int* device_ids, int n_devices, int64_t n_rows, int64_t n_cols, const int64_t* indptr,
+                           const int32_t* indices, const double* values, int32_t k, double doc_concentration,
+                           double topic_concentration, int state_dtype, stc_em_group** out) {
   return guard([&] {
     STC_REQUIRE(device_ids && out, "device_ids/out");
-    // stc_em_create's checks, here so that every member passes or none starts
+    // stc_em_create_as's checks, here so that every member passes or none starts
+    STC_REQUIRE(state_dtype == STC_F64 || state_dtype == STC_F32, "em: the state dtype must be STC_F64 or STC_F32");
     STC_REQUIRE(k >= 2 && k <= 1024, "em: 2 <= k <= 1024");
     check_host_csr(n_rows, n_cols, indptr, indices, values);
     STC_REQUIRE(n_rows < (int64_t(1) << 31) - 1 && n_cols < (int64_t(1) << 31) - 1 && indptr[n_rows] < (int64_t(1) << 31) - 1,
@@ -72,7 +73,8 @@ int stc_em_group_create(const int* device_ids, int n_devices, int64_t n_rows, in
         stc_dcsr* d;
         ~Free() { (void)stc_dcsr_free(d); }
       } free_shard{d};  // the member copies what it needs
-      g->em[(size_t)i] = em::member_create(*c, *d, k, doc_concentration, topic_concentration, g->edge0[(size_t)i]);
+      g->em[(size_t)i] =
+          em::member_create(*c, *d, k, doc_concentration, topic_concentration, state_dtype, g->edge0[(size_t)i]);
     });
     g->k = k;
     g->D = n_rows;
@@ -80,6 +82,13 @@ int stc_em_group_create(const int* device_ids, int n_devices, int64_t n_rows, in
     member_ok(stc_em_get_state(g->em[0], nullptr, nullptr, nullptr, &g->alpha, &g->eta));
     *out = g.release();
   });
+}
+
+int stc_em_group_create(const int* device_ids, int n_devices, int64_t n_rows, int64_t n_cols, const int64_t* indptr,
+                        const int32_t* indices, const double* values, int32_t k, double doc_concentration,
+                        double topic_concentration, stc_em_group** out) {
+  return stc_em_group_create_as(device_ids, n_devices, n_rows, n_cols, indptr, indices, values, k, doc_concentration,
+                                topic_concentration, STC_F64, out);
 }
 
 int stc_em_group_destroy(stc_em_group* g) {

@@ -16,9 +16,10 @@ namespace em {
 
 // collective.  pos_base: the number of edges (non-zero entries) in the earlier shards, so that the RNG keys of
 // init_random continue the global CSR order.  All-reduces the column degrees: a term vertex exists iff any
-// member has an edge of it.
+// member has an edge of it.  state_dtype (STC_F64 | STC_F32): how the member stores N_dk / N_wk, and the type
+// its N_wk' is all-reduced in.
 stc_em* member_create(Ctx& c, const DCsr& shard, int32_t k, double doc_concentration, double topic_concentration,
-                      int64_t pos_base);
+                      int state_dtype, int64_t pos_base);
 void member_init_random(stc_em& m, uint64_t seed);  // collective
 // doc_topics: the member's own rows; both arrays already checked non-negative by the group
 void member_set_state(stc_em& m, const double* doc_topics, const double* term_topics);

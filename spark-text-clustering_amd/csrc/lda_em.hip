@@ -22,9 +22,15 @@
 // N_wk' (a term without a local edge: a 0 row), the members' N_wk' are all-reduced, and N_k / inv follow on
 // every member from the same sum.  The RNG keys of kInit continue the global CSR order (pos_base), and a
 // term vertex exists iff any member has an edge of it (gdeg, all-reduced once at create).
+//
+// State storage (stc_em_create_as): N_dk / N_wk are double or float arrays.  The kernels that touch them are
+// templates on that type; a load widens to double, a store of a new element rounds it once, and everything
+// else — counts, α, η, N_k, inv, γ, accumulators, partials, the scalars — is fp64 in the same order in both
+// instantiations.  N_k is the fp64 column sum of the stored N_wk.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <vector>
 
 #include "collectives.h"
 #include "lda_em.h"
@@ -65,13 +71,16 @@ struct SideView {
 
 enum Mode { kUpdate = 0, kLogLik = 1, kInit = 2, kAssign = 3 };
 
+// T: the state's storage type (double, or float for an STC_F32 handle).  A load widens to double, the store of
+// a new count rounds it to T (once); everything between is fp64 in both instantiations.
+template <typename T>
 struct PassArgs {
   SideView g;
-  const double* own;    // n×k counts of this orientation's vertices
-  const double* other;  // the gathered side's counts
+  const T* own;         // n×k counts of this orientation's vertices
+  const T* other;       // the gathered side's counts
   double own_add, other_add;  // α−1 / η−1 (as fits the side)
   const double* inv;    // k: 1 / (N_k + V(η−1))
-  double* out;          // n×k new counts (vertices with one chunk)
+  T* out;               // n×k new counts (vertices with one chunk)
   double* partial;      // n_multi×k (chunks of the others)
   double* scalar;       // kLogLik: one value per chunk
   uint64_t seed;        // kInit
@@ -85,8 +94,18 @@ struct PassArgs {
 // same number in both orientations (one rounding, commutative), so both passes see the same γ.
 // kAssign (rows only) keeps no sum: per edge the first j with the largest factor, the factor formed as kUpdate
 // forms it.  A padding lane or an empty slot carries −1, below every real factor (α, η > 1 make them > 0).
-template <int KP, int NS, int MODE>
-__global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
+// The fp32 pass stores through two element sizes (T out, double partial), and the compiler kept the byte
+// offsets of both and v·k alive across the edge loop: 2 VGPRs more than the fp64 pass, which at 256 topics
+// is the step from 7 waves per SIMD to 6.  refresh() hides a value's origin there, so the store addresses
+// are formed after the loop.  The fp64 instantiation is left as it was.
+template <typename T, typename X>
+__device__ inline X refresh(X x) {
+  if constexpr (sizeof(T) == 4) asm volatile("" : "+v"(x));
+  return x;
+}
+
+template <typename T, int KP, int NS, int MODE>
+__global__ __launch_bounds__(256) void k_em_pass(const PassArgs<T> a) {
   const int lane = threadIdx.x & 63;
   const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= a.g.n_chunks) return;  // wave-uniform
@@ -102,7 +121,7 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
   for (int i = 0; i < NS; ++i) {
     const int j = j0 + 64 * i;
     const bool live = j < k;
-    own[i] = (MODE != kInit && live) ? a.own[v * k + j] + a.own_add : 0.0;
+    own[i] = (MODE != kInit && live) ? (double)a.own[v * k + j] + a.own_add : 0.0;
     inv[i] = (MODE != kInit && live) ? a.inv[j] : 0.0;
     acc[i] = 0.0;
   }
@@ -121,10 +140,10 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
     const int64_t o = valid ? (int64_t)a.g.idx[ed] : 0;
     if (MODE == kAssign) {
       // every lane loads (a padding lane the last topic, an empty slot row 0), so the NS loads issue together
-      const double* row = a.other + o * k;
+      const T* row = a.other + o * k;
       double x[NS];
 #pragma unroll
-      for (int i = 0; i < NS; ++i) x[i] = row[min(j0 + 64 * i, k - 1)];
+      for (int i = 0; i < NS; ++i) x[i] = (double)row[min(j0 + 64 * i, k - 1)];
       double best = -1.0;
       int bj = j0;
 #pragma unroll
@@ -160,7 +179,7 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
 #pragma unroll
       for (int i = 0; i < NS; ++i) {
         const int j = j0 + 64 * i;
-        g[i] = (valid && j < k) ? (own[i] * (a.other[o * k + j] + a.other_add)) * inv[i] : 0.0;
+        g[i] = (valid && j < k) ? (own[i] * ((double)a.other[o * k + j] + a.other_add)) * inv[i] : 0.0;
         sum += g[i];
       }
     }
@@ -187,19 +206,29 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs a) {
 #pragma unroll
     for (int off = KP; off < 64; off <<= 1) acc[i] += __shfl_xor(acc[i], off, 64);
   }
-  double* dst = nch == 1 ? a.out + v * k : a.partial + (a.g.moff[v] + (c - c0)) * k;
-  if (slot == 0) {
+  if (slot != 0) return;
+  const int js = refresh<T>(j0);
+  if (nch == 1) {  // the vertex's whole sum: stored as the state stores it
+    T* dst = a.out + refresh<T>(v) * k;
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-      const int j = j0 + 64 * i;
+      const int j = js + 64 * i;
+      if (j < k) dst[j] = (T)acc[i];
+    }
+  } else {
+    double* dst = a.partial + (a.g.moff[v] + (c - c0)) * k;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const int j = js + 64 * i;
       if (j < k) dst[j] = acc[i];
     }
   }
 }
 
 // out[v] = Σ partials of v in chunk order (vertices with several chunks), 0 (vertices without an edge)
+template <typename T>
 __global__ void k_em_fixup(const int64_t* __restrict__ choff, const int64_t* __restrict__ moff,
-                           const double* __restrict__ partial, double* __restrict__ out, int64_t n, int k) {
+                           const double* __restrict__ partial, T* __restrict__ out, int64_t n, int k) {
   const int64_t total = n * k;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t v = t / k;
@@ -209,7 +238,7 @@ __global__ void k_em_fixup(const int64_t* __restrict__ choff, const int64_t* __r
     double s = 0.0;
     const double* p = partial + moff[v] * k + j;
     for (int64_t l = 0; l < nch; ++l) s += p[l * k];
-    out[t] = s;
+    out[t] = (T)s;
   }
 }
 
@@ -219,12 +248,13 @@ __device__ inline bool has_vertex(const int64_t* __restrict__ ptr, const int64_t
 }
 
 // rows of vertices without an edge ← 0 (an injected state keeps to the graph's vertices)
-__global__ void k_em_mask(const int64_t* __restrict__ ptr, const int64_t* __restrict__ deg, double* __restrict__ x,
+template <typename T>
+__global__ void k_em_mask(const int64_t* __restrict__ ptr, const int64_t* __restrict__ deg, T* __restrict__ x,
                           int64_t n, int k) {
   const int64_t total = n * k;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t v = t / k;
-    if (!has_vertex(ptr, deg, v)) x[t] = 0.0;
+    if (!has_vertex(ptr, deg, v)) x[t] = (T)0;
   }
 }
 
@@ -235,8 +265,9 @@ __global__ void k_em_degree(const int64_t* __restrict__ ptr, int64_t n, int64_t*
 }
 
 // N_k, level 1: block b sums rows [b·kSumRows, (b+1)·kSumRows) per topic — tpr lanes across the topics,
-// 256/tpr row streams folded in stream order
-__global__ __launch_bounds__(256) void k_em_colsum1(const double* __restrict__ x, int64_t n, int k, int tpr,
+// 256/tpr row streams folded in stream order.  The sum is fp64 over the stored values of either storage type.
+template <typename T>
+__global__ __launch_bounds__(256) void k_em_colsum1(const T* __restrict__ x, int64_t n, int k, int tpr,
                                                     double* __restrict__ part) {
   __shared__ double red[256];
   const int j0 = threadIdx.x % tpr, sub = threadIdx.x / tpr, S = 256 / tpr;
@@ -245,7 +276,7 @@ __global__ __launch_bounds__(256) void k_em_colsum1(const double* __restrict__ x
     const int j = jb + j0;
     double s = 0.0;
     if (j < k)
-      for (int64_t r = r0 + sub; r < r1; r += S) s += x[r * k + j];
+      for (int64_t r = r0 + sub; r < r1; r += S) s += (double)x[r * k + j];
     red[threadIdx.x] = s;
     __syncthreads();
     if (sub == 0 && j < k) {
@@ -297,20 +328,21 @@ __global__ __launch_bounds__(256) void k_em_sum2(const double* __restrict__ part
 }
 
 // logPrior's per-vertex term Σ_j ln(·): terms ln φ_w[j] (inv given), documents ln θ_d[j]; 0 without an edge
+template <typename T>
 __global__ void k_em_prior(const int64_t* __restrict__ ptr, const int64_t* __restrict__ deg,
-                           const double* __restrict__ x, int64_t n, int k, double add, const double* __restrict__ inv,
+                           const T* __restrict__ x, int64_t n, int k, double add, const double* __restrict__ inv,
                            double* __restrict__ out) {
   const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= n) return;
   double s = 0.0;
   if (has_vertex(ptr, deg, v)) {
-    const double* row = x + v * k;
+    const T* row = x + v * k;
     if (inv) {
-      for (int j = 0; j < k; ++j) s += log((row[j] + add) * inv[j]);
+      for (int j = 0; j < k; ++j) s += log(((double)row[j] + add) * inv[j]);
     } else {
       double t = 0.0;
-      for (int j = 0; j < k; ++j) t += row[j] + add;
-      for (int j = 0; j < k; ++j) s += log((row[j] + add) / t);
+      for (int j = 0; j < k; ++j) t += (double)row[j] + add;
+      for (int j = 0; j < k; ++j) s += log(((double)row[j] + add) / t);
     }
   }
   out[v] = s;
@@ -406,13 +438,13 @@ int pow2_at_least(int k) {
   return p;
 }
 
-template <int MODE>
-void launch_pass(hipStream_t s, const PassArgs& a) {
+template <typename T, int MODE>
+void launch_pass(hipStream_t s, const PassArgs<T>& a) {
   if (a.g.n_chunks == 0) return;
   const unsigned grid = blocks_for(a.g.n_chunks, 4);
   const int kp = pow2_at_least(a.k);
 #define STC_EM_CASE(KP, NS)                                \
-  k_em_pass<KP, NS, MODE><<<grid, 256, 0, s>>>(a);         \
+  k_em_pass<T, KP, NS, MODE><<<grid, 256, 0, s>>>(a);      \
   break
   switch (kp) {
     case 2: STC_EM_CASE(2, 1);
@@ -447,7 +479,8 @@ struct stc_em {
   bool has_state = false;
   int cur = 0;           // which of the two state copies is current
   Side rows, cols;
-  DevBuf ndk[2], nwk[2]; // D×k, V×k
+  int dtype = STC_F64;   // how N_dk / N_wk are stored: STC_F64, or STC_F32 (rounded when stored, read widened)
+  DevBuf ndk[2], nwk[2]; // D×k, V×k of dtype
   DevBuf nk, inv;        // k
   DevBuf partial;        // max(rows.n_multi, cols.n_multi)×k
   DevBuf sum_part;       // first-level partials of the N_k and scalar reductions
@@ -492,30 +525,41 @@ void build_chunks(Ctx& c, Side& g, DevBuf& t0, DevBuf& t1, DevBuf& scan_tmp) {
   }
 }
 
+// the host code below is written once over the storage type: f(T{}) with T = double or float
+template <typename F>
+void by_state_type(const stc_em& m, F&& f) {
+  if (m.dtype == STC_F32) f(float{});
+  else f(double{});
+}
+size_t state_elem(const stc_em& m) { return m.dtype == STC_F32 ? sizeof(float) : sizeof(double); }
+
 // N_k and the per-iteration constants of state copy `which`, on the device
 void refresh_totals(stc_em& m, int which) {
   hipStream_t s = m.ctx->stream;
   const int64_t nb = ceil_div(m.V, kSumRows);
   const int tpr = std::min(pow2_at_least(m.k), 256);
-  k_em_colsum1<<<(unsigned)nb, 256, 0, s>>>(m.nwk[which].as<double>(), m.V, m.k, tpr, m.sum_part.as<double>());
+  by_state_type(m, [&](auto t) {
+    using T = decltype(t);
+    k_em_colsum1<T><<<(unsigned)nb, 256, 0, s>>>(m.nwk[which].as<T>(), m.V, m.k, tpr, m.sum_part.as<double>());
+  });
   KERNEL_CHECK();
   k_em_colsum2<<<1, 256, 0, s>>>(m.sum_part.as<double>(), nb, m.k, (double)m.V * (m.eta - 1.0), m.nk.as<double>(),
                                  m.inv.as<double>());
   KERNEL_CHECK();
 }
 
-template <int MODE>
-void run_side(stc_em& m, bool row_side, int from, int to, uint64_t seed) {
+template <typename T, int MODE>
+void run_side_as(stc_em& m, bool row_side, int from, int to, uint64_t seed) {
   hipStream_t s = m.ctx->stream;
   const Side& g = row_side ? m.rows : m.cols;
-  PassArgs a{};
+  PassArgs<T> a{};
   a.g = view(g, !row_side);
-  a.own = (row_side ? m.ndk[from] : m.nwk[from]).as<double>();
-  a.other = (row_side ? m.nwk[from] : m.ndk[from]).as<double>();
+  a.own = (row_side ? m.ndk[from] : m.nwk[from]).as<T>();
+  a.other = (row_side ? m.nwk[from] : m.ndk[from]).as<T>();
   a.own_add = row_side ? m.alpha - 1.0 : m.eta - 1.0;
   a.other_add = row_side ? m.eta - 1.0 : m.alpha - 1.0;
   a.inv = m.inv.as<double>();
-  double* out = (row_side ? m.ndk[to] : m.nwk[to]).as<double>();
+  T* out = (row_side ? m.ndk[to] : m.nwk[to]).as<T>();
   a.out = out;
   a.partial = m.partial.as<double>();
   a.scalar = m.scalar.as<double>();
@@ -523,12 +567,16 @@ void run_side(stc_em& m, bool row_side, int from, int to, uint64_t seed) {
   a.pos_base = m.pos_base;
   a.k = m.k;
   a.assign = m.assign.as<int32_t>();
-  launch_pass<MODE>(s, a);
+  launch_pass<T, MODE>(s, a);
   if (MODE != kLogLik && MODE != kAssign && g.n > 0) {
-    k_em_fixup<<<strided_blocks(g.n * m.k), 256, 0, s>>>(g.choff.as<int64_t>(), g.moff.as<int64_t>(),
-                                                        m.partial.as<double>(), out, g.n, m.k);
+    k_em_fixup<T><<<strided_blocks(g.n * m.k), 256, 0, s>>>(g.choff.as<int64_t>(), g.moff.as<int64_t>(),
+                                                           m.partial.as<double>(), out, g.n, m.k);
     KERNEL_CHECK();
   }
+}
+template <int MODE>
+void run_side(stc_em& m, bool row_side, int from, int to, uint64_t seed) {
+  by_state_type(m, [&](auto t) { run_side_as<decltype(t), MODE>(m, row_side, from, to, seed); });
 }
 
 void sum_to(stc_em& m, const double* x, int64_t n, double* out) {
@@ -554,14 +602,18 @@ void require_state(const stc_em& m) {
 }
 const int64_t* global_degrees(const stc_em& m) { return m.gdeg.p ? m.gdeg.as<int64_t>() : nullptr; }
 
-// a member's N_wk' holds the messages of its own edges: the sum over the members is the graph's
+// a member's N_wk' holds the messages of its own edges: the sum over the members is the graph's (fp32 state:
+// the members' stored, rounded partials are added in fp32)
 void reduce_terms(stc_em& m, int which) {
-  if (m.member && m.ctx->coll()) coll_all_reduce(*m.ctx, m.nwk[which].p, (size_t)(m.V * m.k), ncclFloat64, m.ctx->stream);
+  if (m.member && m.ctx->coll())
+    coll_all_reduce(*m.ctx, m.nwk[which].p, (size_t)(m.V * m.k), m.dtype == STC_F32 ? ncclFloat32 : ncclFloat64,
+                    m.ctx->stream);
 }
 
 stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, double topic_concentration,
-               bool as_member = false, int64_t pos_base = 0) {
+               int state_dtype, bool as_member = false, int64_t pos_base = 0) {
   require_idle_single(c, as_member);
+  STC_REQUIRE(state_dtype == STC_F64 || state_dtype == STC_F32, "em: the state dtype must be STC_F64 or STC_F32");
   STC_REQUIRE(in.dtype == STC_F64, "em: the corpus values must be STC_F64");
   STC_REQUIRE(k >= 2 && k <= 1024, "em: 2 <= k <= 1024");
   STC_REQUIRE(in.rows >= 0 && in.cols > 0, "em: corpus shape");
@@ -579,6 +631,7 @@ stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, doub
   m->V = in.cols;
   m->alpha = alpha;
   m->eta = eta;
+  m->dtype = state_dtype;
   const int64_t nnz = in.nnz;
 
   // 1. the edges: entries whose value is not 0, in CSR order
@@ -645,8 +698,8 @@ stc_em* create(Ctx& c, const DCsr& in, int32_t k, double doc_concentration, doub
   // 4. state and scratch
   const int64_t kk = k;
   for (int i = 0; i < 2; ++i) {
-    m->ndk[i].reserve(8 * std::max<int64_t>(m->D * kk, 1));
-    m->nwk[i].reserve(8 * std::max<int64_t>(m->V * kk, 1));
+    m->ndk[i].reserve(state_elem(*m) * std::max<int64_t>(m->D * kk, 1));
+    m->nwk[i].reserve(state_elem(*m) * std::max<int64_t>(m->V * kk, 1));
   }
   m->nk.reserve(8 * kk);
   m->inv.reserve(8 * kk);
@@ -700,14 +753,24 @@ void set_state(stc_em& m, const double* doc_topics, const double* term_topics, b
   m.ctx->use();
   hipStream_t s = m.ctx->stream;
   const int64_t nd = m.D * m.k, nw = m.V * m.k;
-  if (nd) HIP_CHECK(hipMemcpyAsync(m.ndk[0].p, doc_topics, 8 * nd, hipMemcpyHostToDevice, s));
-  HIP_CHECK(hipMemcpyAsync(m.nwk[0].p, term_topics, 8 * nw, hipMemcpyHostToDevice, s));
-  if (nd) {
-    k_em_mask<<<strided_blocks(nd), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), nullptr, m.ndk[0].as<double>(), m.D, m.k);
-    KERNEL_CHECK();
+  // fp32 state: rounded to nearest on the host (the mask only writes zeros, so its order against the rounding
+  // does not matter); the narrow copies live until the stream has been waited for
+  std::vector<float> nd32, nw32;
+  const void *src_d = doc_topics, *src_w = term_topics;
+  if (m.dtype == STC_F32) {
+    nd32.assign(doc_topics, doc_topics + nd);
+    nw32.assign(term_topics, term_topics + nw);
+    src_d = nd32.data();
+    src_w = nw32.data();
   }
-  k_em_mask<<<strided_blocks(nw), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), global_degrees(m), m.nwk[0].as<double>(), m.V,
-                                               m.k);
+  const size_t es = state_elem(m);
+  if (nd) HIP_CHECK(hipMemcpyAsync(m.ndk[0].p, src_d, es * nd, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(m.nwk[0].p, src_w, es * nw, hipMemcpyHostToDevice, s));
+  by_state_type(m, [&](auto t) {
+    using T = decltype(t);
+    if (nd) k_em_mask<T><<<strided_blocks(nd), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), nullptr, m.ndk[0].as<T>(), m.D, m.k);
+    k_em_mask<T><<<strided_blocks(nw), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), global_degrees(m), m.nwk[0].as<T>(), m.V, m.k);
+  });
   KERNEL_CHECK();
   m.cur = 0;
   refresh_totals(m, 0);
@@ -722,9 +785,19 @@ void get_state(stc_em& m, double* doc_topics, double* term_topics, double* total
   require_state(m);
   m.ctx->use();
   hipStream_t s = m.ctx->stream;
-  if (doc_topics && m.D) HIP_CHECK(hipMemcpyAsync(doc_topics, m.ndk[m.cur].p, 8 * m.D * m.k, hipMemcpyDeviceToHost, s));
-  if (term_topics) HIP_CHECK(hipMemcpyAsync(term_topics, m.nwk[m.cur].p, 8 * m.V * m.k, hipMemcpyDeviceToHost, s));
+  const int64_t nd = doc_topics ? m.D * m.k : 0, nw = term_topics ? m.V * m.k : 0;
   if (totals) HIP_CHECK(hipMemcpyAsync(totals, m.nk.p, 8 * m.k, hipMemcpyDeviceToHost, s));
+  if (m.dtype == STC_F32) {  // the stored values widened on the host, which is exact
+    std::vector<float> nd32((size_t)nd), nw32((size_t)nw);
+    if (nd) HIP_CHECK(hipMemcpyAsync(nd32.data(), m.ndk[m.cur].p, 4 * nd, hipMemcpyDeviceToHost, s));
+    if (nw) HIP_CHECK(hipMemcpyAsync(nw32.data(), m.nwk[m.cur].p, 4 * nw, hipMemcpyDeviceToHost, s));
+    wait_stream(*m.ctx, s);
+    std::copy(nd32.begin(), nd32.end(), doc_topics);
+    std::copy(nw32.begin(), nw32.end(), term_topics);
+    return;
+  }
+  if (nd) HIP_CHECK(hipMemcpyAsync(doc_topics, m.ndk[m.cur].p, 8 * nd, hipMemcpyDeviceToHost, s));
+  if (nw) HIP_CHECK(hipMemcpyAsync(term_topics, m.nwk[m.cur].p, 8 * nw, hipMemcpyDeviceToHost, s));
   wait_stream(*m.ctx, s);
 }
 
@@ -756,13 +829,19 @@ void log_likelihood_parts(stc_em& m, bool want_ll, bool want_prior, double h[3],
     sum_to(m, m.scalar.as<double>(), m.rows.n_chunks, res);
   }
   if (want_prior) {
-    k_em_prior<<<blocks_for(m.V), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), global_degrees(m), m.nwk[m.cur].as<double>(), m.V,
-                                               m.k, m.eta - 1.0, m.inv.as<double>(), m.scalar.as<double>());
+    by_state_type(m, [&](auto t) {
+      using T = decltype(t);
+      k_em_prior<T><<<blocks_for(m.V), 256, 0, s>>>(m.cols.ptr.as<int64_t>(), global_degrees(m), m.nwk[m.cur].as<T>(), m.V,
+                                                    m.k, m.eta - 1.0, m.inv.as<double>(), m.scalar.as<double>());
+    });
     KERNEL_CHECK();
     sum_to(m, m.scalar.as<double>(), m.V, res + 1);
     if (m.D > 0) {
-      k_em_prior<<<blocks_for(m.D), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), nullptr, m.ndk[m.cur].as<double>(), m.D, m.k,
-                                                 m.alpha - 1.0, nullptr, m.scalar.as<double>());
+      by_state_type(m, [&](auto t) {
+        using T = decltype(t);
+        k_em_prior<T><<<blocks_for(m.D), 256, 0, s>>>(m.rows.ptr.as<int64_t>(), nullptr, m.ndk[m.cur].as<T>(), m.D, m.k,
+                                                      m.alpha - 1.0, nullptr, m.scalar.as<double>());
+      });
       KERNEL_CHECK();
     }
     sum_to(m, m.scalar.as<double>(), m.D, res + 2);
@@ -808,8 +887,8 @@ void shape(const stc_em& m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t
 
 // ---- the member side of an stc_em_group (lda_em.h) --------------------------------------------------
 stc_em* member_create(Ctx& c, const DCsr& shard, int32_t k, double doc_concentration, double topic_concentration,
-                      int64_t pos_base) {
-  return create(c, shard, k, doc_concentration, topic_concentration, true, pos_base);
+                      int state_dtype, int64_t pos_base) {
+  return create(c, shard, k, doc_concentration, topic_concentration, state_dtype, true, pos_base);
 }
 void member_init_random(stc_em& m, uint64_t seed) { init_random(m, seed, true); }
 void member_set_state(stc_em& m, const double* doc_topics, const double* term_topics) {
@@ -837,12 +916,24 @@ void member_wait(stc_em& m) {
 extern "C" {
 
 // ---- C ABI ---------------------------------------------------------------------------------
-int stc_em_create(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
-                  double topic_concentration, stc_em** out) {
+int stc_em_create_as(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
+                     double topic_concentration, int state_dtype, stc_em** out) {
   return guard([&] {
     STC_REQUIRE(ctx && corpus && out, "ctx/corpus/out");
     STC_REQUIRE(corpus->ctx == ctx, "the corpus belongs to another stc_ctx");
-    *out = em::create(*ctx, *corpus, k, doc_concentration, topic_concentration);
+    *out = em::create(*ctx, *corpus, k, doc_concentration, topic_concentration, state_dtype);
+  });
+}
+
+int stc_em_create(stc_ctx* ctx, const stc_dcsr* corpus, int32_t k, double doc_concentration,
+                  double topic_concentration, stc_em** out) {
+  return stc_em_create_as(ctx, corpus, k, doc_concentration, topic_concentration, STC_F64, out);
+}
+
+int stc_em_state_dtype(const stc_em* m, int* dtype_out) {
+  return guard([&] {
+    STC_REQUIRE(m && dtype_out, "em/dtype_out");
+    *dtype_out = m->dtype;
   });
 }
 

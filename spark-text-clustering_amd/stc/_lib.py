@@ -142,6 +142,8 @@ SIGNATURES = {
     "stc_lda_counters": (_int, [_p, _pi64]),
     "stc_lda_kernel_counts": (_int, [_p, _pi64]),
     "stc_em_create": (_int, [_p, _p, _i32, _dbl, _dbl, C.POINTER(_p)]),
+    "stc_em_create_as": (_int, [_p, _p, _i32, _dbl, _dbl, _int, C.POINTER(_p)]),
+    "stc_em_state_dtype": (_int, [_p, _pi32]),
     "stc_em_destroy": (_int, [_p]),
     "stc_em_shape": (_int, [_p, _pi32, _pi64, _pi64, _pi64]),
     "stc_em_init_random": (_int, [_p, _u64]),
@@ -169,6 +171,8 @@ SIGNATURES = {
     "stc_group_bound": (_int, [_p, _i64, _i64, _pi64, _pi32, _pdbl, _u64, _i64, _pdbl, _pdbl, _pdbl, _pdbl, _pdbl]),
     "stc_group_topic_distribution": (_int, [_p, _i64, _i64, _pi64, _pi32, _pdbl, _u64, _i64, _pdbl, _pdbl]),
     "stc_em_group_create": (_int, [_pi32, _int, _i64, _i64, _pi64, _pi32, _pdbl, _i32, _dbl, _dbl, C.POINTER(_p)]),
+    "stc_em_group_create_as": (_int, [_pi32, _int, _i64, _i64, _pi64, _pi32, _pdbl, _i32, _dbl, _dbl, _int,
+                                      C.POINTER(_p)]),
     "stc_em_group_destroy": (_int, [_p]),
     "stc_em_group_size": (_int, [_p, _pi32]),
     "stc_em_group_transport": (_int, [_p, _pi32]),

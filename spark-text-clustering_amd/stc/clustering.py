@@ -360,21 +360,43 @@ class LdaGroup:
         self.close()
 
 
+_EM_DTYPES = {"f64": L.STC_F64, "float64": L.STC_F64, "f32": L.STC_F32, "float32": L.STC_F32}
+
+
+def _em_dtype(dtype):
+    """the state dtype code of an EM handle: "f64" or "f32" (EM has no mixed mode)"""
+    if dtype not in _EM_DTYPES:
+        raise ValueError(f"EM state dtype must be 'f64' or 'f32', but was {dtype!r}")
+    return _EM_DTYPES[dtype]
+
+
+def _em_state_dtype(lib, em_handle):
+    """an stc_em's (a group member's) state dtype, read back from the library"""
+    t = C.c_int32()
+    L.check(lib.stc_em_state_dtype(em_handle, C.byref(t)))
+    return {L.STC_F64: "f64", L.STC_F32: "f32"}[t.value]
+
+
 class EmHandle:
     """Owns one stc_em: the EM optimizer's bipartite graph (built once from ``corpus``, which may be freed
     afterwards) and its state N_dk (D×k), N_wk (V×k), N_k on the GPU.  ``doc_concentration`` /
-    ``topic_concentration``: −1 picks Spark's EM defaults 50/k + 1 and 1.1, anything else must be > 1."""
+    ``topic_concentration``: −1 picks Spark's EM defaults 50/k + 1 and 1.1, anything else must be > 1.
+    ``dtype``: "f64", or "f32" — N_dk and N_wk stored as fp32 (every new element rounded once, when stored),
+    all arithmetic, N_k and the scores in fp64; the corpus stays STC_F64 and the state travels as float64."""
 
-    def __init__(self, ctx: Context, corpus: DeviceCsr, k, doc_concentration=-1.0, topic_concentration=-1.0):
+    def __init__(self, ctx: Context, corpus: DeviceCsr, k, doc_concentration=-1.0, topic_concentration=-1.0,
+                 dtype="f64"):
         self.ctx = ctx
         self.handle = None
+        code = _em_dtype(dtype)
         h = C.c_void_p()
-        L.check(ctx.lib.stc_em_create(ctx.handle, corpus.handle, int(k), float(doc_concentration),
-                                      float(topic_concentration), C.byref(h)))
+        L.check(ctx.lib.stc_em_create_as(ctx.handle, corpus.handle, int(k), float(doc_concentration),
+                                         float(topic_concentration), code, C.byref(h)))
         self.handle = h
         kk, d, v, e = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
         L.check(ctx.lib.stc_em_shape(h, C.byref(kk), C.byref(d), C.byref(v), C.byref(e)))
         self.k, self.num_docs, self.vocab_size, self.num_edges = kk.value, d.value, v.value, e.value
+        self.dtype = _em_state_dtype(ctx.lib, h)
 
     def init_random(self, seed):
         L.check(self.ctx.lib.stc_em_init_random(self.handle, int(seed) & 0xFFFFFFFFFFFFFFFF))
@@ -438,22 +460,26 @@ class EmGroup:
     sharded by the library (contiguous document ranges balanced by entries; document ids stay global); N_dk is
     kept by the member that owns the document, N_wk and N_k are replicated and all-reduced once per iteration.
     ``devices`` repeating one device runs that decomposition on the one device.  ``EmHandle``'s methods and
-    attributes, over the whole corpus."""
+    attributes, over the whole corpus.  ``dtype`` "f32": every member stores its state as fp32 (``EmHandle``) and
+    N_wk' is all-reduced as fp32."""
 
-    def __init__(self, devices, corpus: CsrMatrix, k, doc_concentration=-1.0, topic_concentration=-1.0):
-        self.lib = L.load()
+    def __init__(self, devices, corpus: CsrMatrix, k, doc_concentration=-1.0, topic_concentration=-1.0, dtype="f64"):
         self.handle = None
+        code = _em_dtype(dtype)
+        self.lib = L.load()
         devs = np.ascontiguousarray(np.asarray(devices, np.int32))
         ip, ix, v = L.as_i64(corpus.indptr), np.ascontiguousarray(corpus.indices, np.int32), L.as_f64(corpus.values)
         h = C.c_void_p()
-        L.check(self.lib.stc_em_group_create(L.ptr(devs, C.c_int32), devs.size, corpus.num_rows, corpus.num_cols,
-                                             L.ptr(ip, C.c_int64), L.ptr(ix, C.c_int32), L.ptr(v, C.c_double), int(k),
-                                             float(doc_concentration), float(topic_concentration), C.byref(h)))
+        L.check(self.lib.stc_em_group_create_as(L.ptr(devs, C.c_int32), devs.size, corpus.num_rows, corpus.num_cols,
+                                                L.ptr(ip, C.c_int64), L.ptr(ix, C.c_int32), L.ptr(v, C.c_double),
+                                                int(k), float(doc_concentration), float(topic_concentration), code,
+                                                C.byref(h)))
         self.handle = h
         self.devices = devs.tolist()
         kk, d, vv, e = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
         L.check(self.lib.stc_em_group_shape(h, C.byref(kk), C.byref(d), C.byref(vv), C.byref(e)))
         self.k, self.num_docs, self.vocab_size, self.num_edges = kk.value, d.value, vv.value, e.value
+        self.dtype = _em_state_dtype(self.lib, self.members()[0][0])
 
     def members(self):
         """[(member stc_em handle, its first corpus row)], for reading only: stc_em_shape, stc_em_get_state"""
@@ -984,10 +1010,11 @@ class MllibLDA:
         """EMLDAOptimizer.initialize, maxIterations × next, getLDAModel (a DistributedLDAModel)"""
         import time
 
+        _em_dtype(self.dtype)  # "mixed" is the online optimizer's: EM has no mixed mode
         alpha, eta = em_concentrations(self.k, self.docConcentration, self.topicConcentration)
         if self.devices is not None:
             host = corpus.download() if isinstance(corpus, DeviceCsr) else corpus
-            em = EmGroup(self.devices, host, self.k, alpha, eta)
+            em = EmGroup(self.devices, host, self.k, alpha, eta, dtype=self.dtype)
             em.init_random(self.seed)
             em.synchronize()
             self.iterationTimes = []
@@ -1003,7 +1030,7 @@ class MllibLDA:
         else:
             dev, host = DeviceCsr.upload(ctx, corpus, L.STC_F64), corpus
         try:
-            em = EmHandle(ctx, dev, self.k, alpha, eta)
+            em = EmHandle(ctx, dev, self.k, alpha, eta, dtype=self.dtype)
         finally:
             if dev is not corpus:
                 dev.free()

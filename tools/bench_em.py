@@ -12,12 +12,13 @@ Per case: --warmup (3) untimed iterations, then --iters (20) timed as ONE enqueu
 synchronisations (an iteration has no host round trip), repeated --repeats (5) times; the line carries the
 median and the spread.  edges·k per second and algorithmic bytes per second follow from the median.
 Algorithmic bytes per iteration = for each of the two passes, the edge arrays once (4 B index + 8 B count
-per edge) plus one gathered k-row (8k B) per edge: 2·E·(12 + 8k).
+per edge) plus one gathered k-row (8k B) per edge: 2·E·(12 + 8k).  With --dtype f32 (the state stored as fp32,
+stc_em_create_as) a gathered row is 4k B: 2·E·(12 + 4k).
 
 The topicAssignments pass (stc_em_topic_assignments with every output NULL: the pass is enqueued, nothing is
 copied out) is timed in the same run under the same discipline, from the state the timed iterations left:
 --warmup untimed passes, --iters passes as one enqueued batch, --repeats times.  Its algorithmic bytes are the
-term index, one gathered k-row and the 4 B result per edge: E·(8 + 8k).  The row pass it is to be read
+term index, one gathered k-row and the 4 B result per edge: E·(8 + 8k), at --dtype f32 E·(8 + 4k).  The row pass it is to be read
 against is one kernel of the iteration; its time comes from a kernel trace of this tool's run.
 
 --devices 0,0 or 0,1,… runs the same cases through an EmGroup (stc_em_group: documents sharded over the members,
@@ -27,7 +28,7 @@ host inside every all-reduce, so it says nothing about scaling.  STC_GROUP_RCCL=
 one-member group over a real RCCL communicator.
 
     python tools/bench_em.py [--case golden|zipf|all] [--iters 20] [--warmup 3] [--repeats 5] [--workers N]
-                             [--devices 0,0]
+                             [--devices 0,0] [--dtype f64|f32]
 """
 import argparse
 import json
@@ -43,18 +44,20 @@ sys.path[:0] = [os.path.join(ROOT, "spark-text-clustering_amd"), ROOT]
 GOLDEN_MODEL = os.path.join(ROOT, "tests", "golden", "LdaModel_EN_1591049082850")
 
 
-def make_handle(stc, ctx, devices, corpus, k, alpha=-1.0, eta=-1.0):
-    """(handle, synchronize): an EmHandle on ctx, or an EmGroup over `devices`"""
+def make_handle(stc, ctx, devices, corpus, k, alpha=-1.0, eta=-1.0, dtype="f64"):
+    """(handle, synchronize): an EmHandle on ctx, or an EmGroup over `devices`.  The default dtype goes through
+    the constructors' own default, so the tool also drives a library from before --dtype existed."""
+    kw = {} if dtype == "f64" else {"dtype": dtype}
     if devices:
-        g = stc.EmGroup(devices, corpus, k, alpha, eta)
+        g = stc.EmGroup(devices, corpus, k, alpha, eta, **kw)
         return g, g.synchronize
     dev = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F64)
-    h = stc.EmHandle(ctx, dev, k, alpha, eta)
+    h = stc.EmHandle(ctx, dev, k, alpha, eta, **kw)
     dev.free()
     return h, ctx.synchronize
 
 
-def golden_case(stc, ctx, devices):
+def golden_case(stc, ctx, devices, dtype):
     m = stc.io.load_distributed(GOLDEN_MODEL)
     src, term, cnt = m["edges"]
     row = np.searchsorted(m["doc_ids"], src)
@@ -62,18 +65,18 @@ def golden_case(stc, ctx, devices):
     indptr = np.zeros(m["doc_ids"].size + 1, np.int64)
     np.cumsum(np.bincount(row, minlength=m["doc_ids"].size), out=indptr[1:])
     corpus = stc.CsrMatrix(indptr, term[order], cnt[order], m["vocab_size"])
-    h, sync = make_handle(stc, ctx, devices, corpus, m["k"], float(m["alpha"][0]), m["eta"])
+    h, sync = make_handle(stc, ctx, devices, corpus, m["k"], float(m["alpha"][0]), m["eta"], dtype)
     h.set_state(m["doc_topics"], m["topics"])
     ref = float(np.median(m["iteration_times"]))
     return h, sync, {"case": "golden", "reference_s_per_iteration": ref,
                "reference_note": "median of the saved model's 50 iterationTimes; unknown PC, Spark local[*]"}
 
 
-def zipf_case(stc, ctx, devices, docs, tokens, vocab, k, workers):
+def zipf_case(stc, ctx, devices, docs, tokens, vocab, k, workers, dtype):
     from stc import synth
 
     corpus = synth.zipf_corpus(docs, tokens, vocab, workers=workers)
-    h, sync = make_handle(stc, ctx, devices, corpus, k)
+    h, sync = make_handle(stc, ctx, devices, corpus, k, dtype=dtype)
     h.init_random(1)
     return h, sync, {"case": "zipf", "docs": docs, "tokens_per_doc": tokens}
 
@@ -110,18 +113,19 @@ def measure(ctx, h, sync, info, iters, warmup, repeats):
         ms.append((time.perf_counter() - t0) * 1e3 / iters)
     med = float(np.median(ms))
     E, k = h.num_edges, h.k
-    algo_bytes = 2.0 * E * (12 + 8 * k)
+    row = (4 if getattr(h, "dtype", "f64") == "f32" else 8) * k  # bytes of one gathered state row
+    algo_bytes = 2.0 * E * (12 + row)
     ll, lp = h.log_likelihood()
     ams = assign_pass_ms(ctx, h, sync, iters, warmup, repeats)
     if hasattr(h, "members"):
         info = dict(info, devices=h.devices, transport=h.transport())
     amed = float(np.median(ams))
-    out = dict(info, n_docs=h.num_docs, vocab=h.vocab_size, k=k, edges=E, iters=iters, warmup=warmup, repeats=repeats,
+    out = dict(info, dtype=getattr(h, "dtype", "f64"), n_docs=h.num_docs, vocab=h.vocab_size, k=k, edges=E, iters=iters, warmup=warmup, repeats=repeats,
                ms_per_iteration=med, ms_per_iteration_min=float(min(ms)), ms_per_iteration_max=float(max(ms)),
                edges_k_per_s=E * k / (med * 1e-3), algorithmic_bytes_per_iteration=algo_bytes,
                algorithmic_bytes_per_s=algo_bytes / (med * 1e-3), log_likelihood=ll, log_prior=lp,
                ms_per_assign_pass=amed, ms_per_assign_pass_min=float(min(ams)), ms_per_assign_pass_max=float(max(ams)),
-               assign_algorithmic_bytes_per_s=E * (8.0 + 8 * k) / (amed * 1e-3))
+               assign_algorithmic_bytes_per_s=E * (8.0 + row) / (amed * 1e-3))
     if "reference_s_per_iteration" in info:
         out["speedup_vs_reference"] = info["reference_s_per_iteration"] / (med * 1e-3)
     return out
@@ -141,14 +145,16 @@ def main():
                    help="corpus-generation processes of the zipf case (1 under a profiler: nothing is forked)")
     p.add_argument("--devices", default="",
                    help="comma-separated device ids of an EmGroup (0,0: two members on device 0); empty: one EmHandle")
+    p.add_argument("--dtype", choices=("f64", "f32"), default="f64",
+                   help="how the handle or group stores N_dk / N_wk (f32: rounded when stored; arithmetic stays fp64)")
     a = p.parse_args()
     import stc
 
     devices = [int(d) for d in a.devices.split(",") if d.strip()]
     ctx = stc.Context.get(0)
     for case in (("golden", "zipf") if a.case == "all" else (a.case,)):
-        h, sync, info = (golden_case(stc, ctx, devices) if case == "golden" else
-                         zipf_case(stc, ctx, devices, a.docs, a.tokens, a.vocab, a.k, a.workers))
+        h, sync, info = (golden_case(stc, ctx, devices, a.dtype) if case == "golden" else
+                         zipf_case(stc, ctx, devices, a.docs, a.tokens, a.vocab, a.k, a.workers, a.dtype))
         print(json.dumps(measure(ctx, h, sync, info, a.iters, a.warmup, a.repeats)), flush=True)
         h.close()
 
