@@ -14,6 +14,9 @@
  *   stc_prep_*                  the reference's own steps behind that lemmatiser: LDAUtil.filterSpecialCharacters,
  *                               OpenNLP SimpleTokenizer, the stop-word filter and OpenNLP PorterStemmer —
  *                               LDAClustering.scala:121-139 (training), :221-238 (scoring)
+ *   stc_swr_*, stc_ngram_tokens [U] ml.feature.StopWordsRemover and ml.feature.NGram, the stages a Spark pipeline puts
+ *                               between its tokenizer and its vectorizer (device tokens in and out);
+ *                               stc_tokenize_tokens is the Tokenizer feeding them
  *   stc_hashing_tf[_dev]        [U] mllib.feature.HashingTF.transform / murmur3Hash — the slot of
  *                               the vocab-indexed counting at LDAClustering.scala:154-167
  *   stc_cv_*                    [U] ml.feature.CountVectorizer / CountVectorizerModel — the vocabulary-indexed
@@ -267,11 +270,49 @@ int stc_prep_tokens(stc_ctx* ctx, const stc_prep* prep, const uint8_t* text, int
 /* sizes of device tokens (any may be NULL), and their copy to the host: utf8_out[n_bytes], tok_off_out[n_tok+1],
  * doc_off_out[n_docs+1] (any may be NULL) */
 int stc_tokens_shape(const stc_dtok* tokens, int64_t* n_bytes, int64_t* n_tok, int64_t* n_docs);
+/* the longest document's token count the device tokens carry (the vectorizers choose their kernel path from it):
+ * exact for an upload and for every result of the library */
+int stc_tokens_max_doc(const stc_dtok* tokens, int64_t* max_doc_out);
 int stc_tokens_download(stc_ctx* ctx, const stc_dtok* tokens, uint8_t* utf8_out, int64_t* tok_off_out,
                         int64_t* doc_off_out);
 /* the stemmer alone, each token on its own (test hook): utf8_out[n_bytes], tok_off_out[n_tok+1] */
 int stc_stem_tokens(stc_ctx* ctx, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off, int64_t n_tok,
                     uint8_t* utf8_out, int64_t* tok_off_out);
+
+/* ---- Token stages (device tokens in, device tokens out) --------------------------------------
+ * What sits between a tokenizer and a vectorizer in a Spark ML pipeline, without leaving the device: either front end
+ * (stc_tokenize_tokens, stc_prep_tokens, or an upload) feeds either vectorizer (stc_hashing_tf_tokens, stc_cv_*_tokens)
+ * through any chain of these stages.  Every result is an stc_dtok with the invariants of stc_tokens_upload (zero
+ * padding behind the blob, u32 offsets when blob + padding fit in 4 GiB, the longest document's token count), freed
+ * with stc_tokens_free; the input is left as it is.  Every input document keeps its row, possibly empty.
+ * stc_tokenize_tokens: exactly stc_tokenize's tokens (the same lower-casing, the same errors), left on the device.
+ * StopWordsRemover ([U] ml.feature.StopWordsRemover.transform).  Kept tokens keep their order and their original
+ *   bytes.  The list is the caller's (Spark's bundled language lists are not part of this library); duplicates are
+ *   fine, n_stop = 0 keeps everything, and the empty word is legal and drops empty tokens (the Tokenizer makes them).
+ *   Stop words must be well-formed UTF-8 in both modes.
+ *   case_sensitive = 1: a token is dropped iff its bytes equal a stop word's bytes; tokens are not validated.
+ *   case_sensitive = 0 (Spark's default): a token is dropped iff toLowerCase(token) equals toLowerCase(w) for some
+ *   stop word w, toLowerCase being the Tokenizer block's Java 8 root-locale lower-casing applied to the token (or the
+ *   word) as a string of its own: the Final_Sigma context is the token, İ → "i̇" changes the length.  Tokens and stop
+ *   words go through the same device routine, so the two sides cannot drift.  That routine's Final_Sigma rule is the
+ *   Unicode one, not the JVM's BreakIterator-word scan: the two differ when a digit stands between Σ and a cased
+ *   letter ("Α1Σ": Java ς, here σ; parity unpinned, as for stc_tokenize).  Spark lower-cases with a locale parameter
+ *   (the JVM default); this is the root locale, which differs from tr, az and lt only.  In this mode every token must
+ *   be well-formed UTF-8: STC_ERR_INVALID_ARG naming the byte offset in the blob otherwise.
+ * NGram ([U] ml.feature.NGram: sliding(n).withPartial(false).map(_.mkString(" "))).  n >= 1, else
+ *   STC_ERR_INVALID_ARG.  A document of T tokens yields max(T - n + 1, 0) tokens; output token i is input tokens
+ *   i .. i+n-1 joined by one U+0020; empty tokens join as they are (["a", "", "b"], n = 2 → ["a ", " b"]); n = 1 is a
+ *   copy.
+ * At most 2^31-1 input tokens per call.  Bitwise reproducible.  A handle made by another context is
+ * STC_ERR_INVALID_ARG.  Single device: every call on a context connected to other ranks returns STC_ERR_STATE. */
+int stc_tokenize_tokens(stc_ctx* ctx, const uint8_t* text, int64_t n_bytes, const int64_t* text_off /* n_docs+1 */,
+                        int64_t n_docs, stc_dtok** out);
+typedef struct stc_swr stc_swr; /* the stop words' table on the device; belongs to its stc_ctx as an stc_prep does */
+int stc_swr_create(stc_ctx* ctx, const uint8_t* stop_utf8, int64_t n_bytes, const int64_t* stop_off /* n_stop+1 */,
+                   int64_t n_stop, int case_sensitive, stc_swr** out);
+int stc_swr_free(stc_swr* swr); /* valid after stc_destroy of the context */
+int stc_swr_tokens(stc_ctx* ctx, const stc_swr* swr, const stc_dtok* in, stc_dtok** out);
+int stc_ngram_tokens(stc_ctx* ctx, const stc_dtok* in, int32_t n, stc_dtok** out);
 
 /* ---- IDF (K3 df count, K4 idf, K5 transform) ---------------------------------------------
  * df_j = #rows with value_j > 0, m = #rows (summed over all ranks when connected);

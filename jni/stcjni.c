@@ -859,6 +859,53 @@ JNIEXPORT jlong JNICALL FN(prepTokens)(JNIEnv* env, jclass c, jlong ctx, jlong p
   return (jlong)(intptr_t)out;
 }
 
+/* ---- token stages (device tokens in and out: Tokenizer result, StopWordsRemover, NGram) ------------------- */
+/* document d = text[textOff[d], textOff[d+1]); the Tokenizer's tokens as device tokens (tokensFree) */
+JNIEXPORT jlong JNICALL FN(tokenizeTokens)(JNIEnv* env, jclass c, jlong ctx, jbyteArray text, jlongArray text_off) {
+  stc_dtok* out = NULL;
+  if (!text_off || LEN(text_off) < 1) {
+    throw_iae(env, "tokenizeTokens: textOff needs nDocs + 1 entries");
+    return 0;
+  }
+  jbyte* t = PIN(jbyte, Byte, text);
+  jlong* to = PIN(jlong, Long, text_off);
+  int st = stc_tokenize_tokens(CTX(ctx), (const uint8_t*)t, LEN(text), (const int64_t*)to, LEN(text_off) - 1, &out);
+  UNPIN(Long, text_off, to, JNI_ABORT);
+  UNPIN(Byte, text, t, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+/* stop word j = stopUtf8[stopOff[j], stopOff[j+1]) (stopOff null: none) */
+JNIEXPORT jlong JNICALL FN(swrCreate)(JNIEnv* env, jclass c, jlong ctx, jbyteArray stop_utf8, jlongArray stop_off,
+                                      jboolean case_sensitive) {
+  stc_swr* out = NULL;
+  jbyte* u = PIN(jbyte, Byte, stop_utf8);
+  jlong* so = PIN(jlong, Long, stop_off);
+  int st = stc_swr_create(CTX(ctx), (const uint8_t*)u, LEN(stop_utf8), (const int64_t*)so, stop_off ? LEN(stop_off) - 1 : 0,
+                          case_sensitive ? 1 : 0, &out);
+  UNPIN(Long, stop_off, so, JNI_ABORT);
+  UNPIN(Byte, stop_utf8, u, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT void JNICALL FN(swrFree)(JNIEnv* env, jclass c, jlong swr) { check(env, stc_swr_free((stc_swr*)(intptr_t)swr)); }
+
+/* the tokens without their stop words: new device tokens (tokensFree); the input stays valid */
+JNIEXPORT jlong JNICALL FN(swrTokens)(JNIEnv* env, jclass c, jlong ctx, jlong swr, jlong tokens) {
+  stc_dtok* out = NULL;
+  if (check(env, stc_swr_tokens(CTX(ctx), (const stc_swr*)(intptr_t)swr, (const stc_dtok*)(intptr_t)tokens, &out))) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+/* every run of n consecutive tokens of a document joined by one space: new device tokens (tokensFree) */
+JNIEXPORT jlong JNICALL FN(ngramTokens)(JNIEnv* env, jclass c, jlong ctx, jlong tokens, jint n) {
+  stc_dtok* out = NULL;
+  if (check(env, stc_ngram_tokens(CTX(ctx), (const stc_dtok*)(intptr_t)tokens, n, &out))) return 0;
+  return (jlong)(intptr_t)out;
+}
+
 /* {nBytes, nTok, nDocs} */
 JNIEXPORT jlongArray JNICALL FN(tokensShape)(JNIEnv* env, jclass c, jlong tokens) {
   int64_t s[3] = {0, 0, 0};
@@ -866,6 +913,13 @@ JNIEXPORT jlongArray JNICALL FN(tokensShape)(JNIEnv* env, jclass c, jlong tokens
   jlongArray out = (*env)->NewLongArray(env, 3);
   if (out) (*env)->SetLongArrayRegion(env, out, 0, 3, (const jlong*)s);
   return out;
+}
+
+/* the longest document's token count */
+JNIEXPORT jlong JNICALL FN(tokensMaxDoc)(JNIEnv* env, jclass c, jlong tokens) {
+  int64_t m = 0;
+  if (check(env, stc_tokens_max_doc((const stc_dtok*)(intptr_t)tokens, &m))) return 0;
+  return (jlong)m;
 }
 
 /* every array nullable: utf8Out nBytes, tokOffOut nTok + 1, docOffOut nDocs + 1 */

@@ -156,8 +156,20 @@ public final class StcNative {
   public static native void prepFree(long prep);
   /** document d = text[textOff[d], textOff[d+1]); the result is device tokens (tokensFree) */
   public static native long prepTokens(long ctx, long prep, byte[] text, long[] textOff);
+  /** token stages (stc_tokenize_tokens, stc_swr_*, stc_ngram_tokens): device tokens in, new device tokens out
+   *  (tokensFree each; the input stays valid).  tokenizeTokens: ml.feature.Tokenizer's result left on the device */
+  public static native long tokenizeTokens(long ctx, byte[] text, long[] textOff);
+  /** ml.feature.StopWordsRemover: stop word j = stopUtf8[stopOff[j], stopOff[j+1]); caseSensitive false compares
+   *  Java 8 root-locale lower cases */
+  public static native long swrCreate(long ctx, byte[] stopUtf8, long[] stopOff, boolean caseSensitive);
+  public static native void swrFree(long swr);
+  public static native long swrTokens(long ctx, long swr, long tokens);
+  /** ml.feature.NGram: every run of n consecutive tokens of a document joined by one space */
+  public static native long ngramTokens(long ctx, long tokens, int n);
   /** {nBytes, nTok, nDocs} of device tokens */
   public static native long[] tokensShape(long tokens);
+  /** the longest document's token count of device tokens */
+  public static native long tokensMaxDoc(long tokens);
   /** every array nullable: utf8Out nBytes, tokOffOut nTok + 1, docOffOut nDocs + 1 */
   public static native void tokensDownload(long ctx, long tokens, byte[] utf8Out, long[] tokOffOut, long[] docOffOut);
   /** the stemmer alone, each token on its own: utf8Out utf8.length, tokOffOut tokOff.length */

@@ -220,6 +220,35 @@ int stc_tokenize(stc_ctx* ctx, const uint8_t* text, int64_t n_bytes, const int64
   });
 }
 
+// the tokenizer's result turned into device tokens with the invariants of stc_tokens_upload
+int stc_tokenize_tokens(stc_ctx* ctx, const uint8_t* text, int64_t n_bytes, const int64_t* text_off, int64_t n_docs,
+                        stc_dtok** out) {
+  return guard([&] {
+    STC_REQUIRE(ctx && out, "ctx/out");
+    if (ctx->coll()) throw Error(STC_ERR_STATE, "token stages: the context is connected to other ranks (the token stages are single-device)");
+    ctx->use();
+    hipStream_t s = ctx->stream;
+    Tokens t;
+    run_tokenizer(*ctx, t, text, n_bytes, text_off, n_docs);
+    auto d = new_handle<stc_dtok>(*ctx);
+    HIP_CHECK(hipMemsetAsync(t.utf8.as<uint8_t>() + t.n_bytes, 0, kHashPad, s));  // (reserved by the tokenizer)
+    if (t.n_bytes + kHashPad <= (int64_t(1) << 32)) {
+      d->tok_off.reserve(4 * (t.n_tok + 1));
+      hashing::narrow_offsets(*ctx, t.tok_off.as<int64_t>(), t.n_tok + 1, d->tok_off.as<uint32_t>());
+      d->off32 = true;
+    } else {
+      swap(d->tok_off, t.tok_off);
+    }
+    d->max_doc = stages::longest_doc(*ctx, t.doc_off.as<int64_t>(), n_docs);  // (waits for the stream)
+    swap(d->utf8, t.utf8);
+    swap(d->doc_off, t.doc_off);
+    d->n_bytes = t.n_bytes;
+    d->n_tok = t.n_tok;
+    d->n_docs = n_docs;
+    *out = d.release();
+  });
+}
+
 int stc_tokenize_hashing_tf_dev(stc_ctx* ctx, const uint8_t* text, int64_t n_bytes,
                                 const int64_t* text_off, int64_t n_docs, int32_t num_features,
                                 int binary, int hash_variant, int value_dtype, stc_dcsr** out) {

@@ -37,6 +37,10 @@ struct TokenUpload {  // host tokens copied to the device for one call (features
 };
 void upload_tokens(Ctx& c, TokenUpload& u, const uint8_t* utf8, int64_t n_bytes, const int64_t* tok_off,
                    int64_t n_tok, const int64_t* doc_off, int64_t n_docs);
+namespace stages {
+// the longest document's token count from device document offsets (token_stages.hip); waits for the stream
+int64_t longest_doc(Ctx& c, const int64_t* d_doc_off, int64_t n_docs);
+}  // namespace stages
 inline void swap(DevBuf& a, DevBuf& b) {
   std::swap(a.p, b.p);
   std::swap(a.bytes, b.bytes);

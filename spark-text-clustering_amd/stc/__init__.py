@@ -14,9 +14,10 @@ from .core import Context, CsrMatrix, DeviceCsr
 from .count_vectorizer import CountVectorizer, CountVectorizerModel
 from .feature import IDF, DeviceTokens, HashingTF, IDFModel, Tokenizer, encode_texts, encode_tokens
 from .text_prep import DEFAULT_STRIP_CHARS, PorterStemmer, TextPreprocessor
+from .token_stages import NGram, StopWordsRemover
 
 __all__ = [
-    "Context", "CsrMatrix", "DeviceCsr", "CountVectorizer", "CountVectorizerModel", "HashingTF", "IDF", "IDFModel", "Tokenizer", "DeviceTokens", "TextPreprocessor", "PorterStemmer", "DEFAULT_STRIP_CHARS", "encode_texts", "encode_tokens", "LDA",
+    "Context", "CsrMatrix", "DeviceCsr", "CountVectorizer", "CountVectorizerModel", "HashingTF", "IDF", "IDFModel", "Tokenizer", "DeviceTokens", "TextPreprocessor", "StopWordsRemover", "NGram", "PorterStemmer", "DEFAULT_STRIP_CHARS", "encode_texts", "encode_tokens", "LDA",
     "LDAModel", "DistributedLDAModel", "LdaGroup", "LdaHandle", "EmHandle", "EmGroup", "io", "MllibLDA", "OnlineLDAOptimizer",
     "EMLDAOptimizer", "em_concentrations", "ML_LDA_DEFAULT_SEED", "reference_mini_batch_fraction", "StcError", "StcIllegalArgument", "load", "STC_F32", "STC_F64", "STC_MIXED",
     "STC_HASH_STANDARD", "STC_HASH_SPARK24", "STC_LAYOUT_VK", "STC_LAYOUT_KV", "STC_ERR_INVALID_ARG", "STC_ERR_HIP",

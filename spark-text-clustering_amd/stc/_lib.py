@@ -107,11 +107,17 @@ SIGNATURES = {
     "stc_prep_free": (_int, [_p]),
     "stc_prep_tokens": (_int, [_p, _p, _pu8, _i64, _pi64, _i64, C.POINTER(_p)]),
     "stc_tokens_shape": (_int, [_p, _pi64, _pi64, _pi64]),
+    "stc_tokens_max_doc": (_int, [_p, _pi64]),
     "stc_tokens_download": (_int, [_p, _p, _pu8, _pi64, _pi64]),
     "stc_stem_tokens": (_int, [_p, _pu8, _i64, _pi64, _i64, _pu8, _pi64]),
     "stc_tokenize": (_int, [_p, _pu8, _i64, _pi64, _i64, _pu8, _i64, _pi64, _pi64, _pi64, _pi64]),
     "stc_tokenize_hashing_tf_dev": (_int, [_p, _pu8, _i64, _pi64, _i64, _i32, _int, _int, _int,
                                            C.POINTER(_p)]),
+    "stc_tokenize_tokens": (_int, [_p, _pu8, _i64, _pi64, _i64, C.POINTER(_p)]),
+    "stc_swr_create": (_int, [_p, _pu8, _i64, _pi64, _i64, _int, C.POINTER(_p)]),
+    "stc_swr_free": (_int, [_p]),
+    "stc_swr_tokens": (_int, [_p, _p, _p, C.POINTER(_p)]),
+    "stc_ngram_tokens": (_int, [_p, _p, _i32, C.POINTER(_p)]),
     "stc_idf_fit": (_int, [_p, _p, _i64, _pdbl, _pi64, _pi64]),
     "stc_idf_transform": (_int, [_p, _p, _pdbl, _dbl]),
     "stc_idf_fit_dev": (_int, [_p, _p, _i64, C.POINTER(_p)]),

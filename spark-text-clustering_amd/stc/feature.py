@@ -67,6 +67,14 @@ class DeviceTokens:
         self.n_bytes, self.n_tok, self.n_docs = nb.value, nt.value, nd.value
         return self
 
+    @property
+    def max_doc(self) -> int:
+        """the longest document's token count the device tokens carry (HashingTF and CountVectorizer choose their
+        kernel path from it)"""
+        m = C.c_int64()
+        L.check(self.ctx.lib.stc_tokens_max_doc(self.handle, C.byref(m)))
+        return m.value
+
     def download(self):
         """the (utf8 uint8 blob, tok_off int64[n_tok+1], doc_off int64[n_docs+1]) triple, copied to the host"""
         blob = np.zeros(max(self.n_bytes, 1), np.uint8)
@@ -93,8 +101,10 @@ class Tokenizer:
 
     Mirrors ``org.apache.spark.ml.feature.Tokenizer`` ([U] spark 2.4.3, build.sbt:10):
     ``text.toLowerCase.split("\\s")`` — interior empty tokens kept, trailing ones dropped, a
-    document without whitespace is one token.  Lower-casing covers ASCII and Latin-1; text with
-    characters that need other case tables raises ``ValueError`` (STC_ERR_INVALID_ARG).
+    document without whitespace is one token.  Lower-casing is Java 8's ``String.toLowerCase`` (root
+    locale, Unicode 6.2) for every code point, İ → "i̇" and Σ → ς / σ by its Final_Sigma context
+    included (include/stc.h, "Tokenizer").  ``transform_device`` leaves the tokens on the GPU for
+    StopWordsRemover, NGram, HashingTF or CountVectorizer.
     """
 
     def __init__(self, inputCol=None, outputCol=None, ctx: Context | None = None):
@@ -118,6 +128,14 @@ class Tokenizer:
                                           C.byref(nb), L.ptr(tok_off, C.c_int64), C.byref(nt),
                                           L.ptr(doc_off, C.c_int64)))
         return blob[:nb.value].copy(), tok_off[:nt.value + 1].copy(), doc_off
+
+    def transform_device(self, texts) -> DeviceTokens:
+        """list[str|bytes] → the documents' tokens (exactly ``encode``'s), left resident in HBM"""
+        text, off = encode_texts(texts)
+        h = C.c_void_p()
+        L.check(self.ctx.lib.stc_tokenize_tokens(self.ctx.handle, L.ptr(text, C.c_uint8), text.size,
+                                                 L.ptr(off, C.c_int64), off.size - 1, C.byref(h)))
+        return DeviceTokens.from_handle(self.ctx, h)
 
     def transform(self, texts):
         """list[str] → list[list[str]] (the tokens of each document)."""
