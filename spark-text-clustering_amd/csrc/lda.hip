@@ -358,34 +358,32 @@ __global__ __launch_bounds__(kBlock) void k_estep(EStepArgs<T> a) {
     estep_doc<T, STATS, BOUND, false>(a, smem, slot, mem, row, s0, nnz, e0);
 }
 
+// a kernel's dynamic-LDS limit: kLdsBudget, which holds every launch that keeps block rows in LDS — or, where
+// the fixed arrays alone pass it (fp64 kp > 3408: 24·kp + 128 B, 98,432 B at kp = 4096, lds_rows = 0), their
+// size.  `have` is the kernel's registered limit (0: none yet).
+static void reserve_estep_lds(const void* kern, size_t lds, size_t& have) {
+  if (lds <= have) return;
+  const size_t want = lds > (size_t)kLdsBudget ? lds : (size_t)kLdsBudget;
+  HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want));
+  have = want;
+}
+
 template <typename T>
 void launch_estep(hipStream_t s, const EStepArgs<T>& a, bool stats, bool bound) {
   if (a.n == 0) return;
   const size_t lds = estep_lds_bytes<T>(a.kp, a.lds_rows, a.P);
   const dim3 grid((unsigned)a.n);
   if (stats) {
-    static bool set = false;
-    if (!set) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)k_estep<T, true, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
-      set = true;
-    }
+    static size_t have = 0;
+    reserve_estep_lds((const void*)k_estep<T, true, false>, lds, have);
     k_estep<T, true, false><<<grid, kBlock, lds, s>>>(a);
   } else if (bound) {
-    static bool set = false;
-    if (!set) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)k_estep<T, false, true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
-      set = true;
-    }
+    static size_t have = 0;
+    reserve_estep_lds((const void*)k_estep<T, false, true>, lds, have);
     k_estep<T, false, true><<<grid, kBlock, lds, s>>>(a);
   } else {
-    static bool set = false;
-    if (!set) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)k_estep<T, false, false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBudget));
-      set = true;
-    }
+    static size_t have = 0;
+    reserve_estep_lds((const void*)k_estep<T, false, false>, lds, have);
     k_estep<T, false, false><<<grid, kBlock, lds, s>>>(a);
   }
   KERNEL_CHECK();

@@ -403,6 +403,14 @@ __global__ __launch_bounds__(256) void k_update_alpha(double* __restrict__ alpha
 }
 
 void launch_update_alpha(hipStream_t s, double* alpha, const double* small, int k, double rho) {
+  // gradf and q: 16·k B, 64 KiB at k = 4096 beside the kernel's static words — past the default limit of a
+  // launch from k = 4089, so the largest request (k ≤ 4096, stc_lda_create) is registered once
+  static bool set = false;
+  if (!set) {
+    HIP_CHECK(hipFuncSetAttribute((const void*)k_update_alpha, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(2 * sizeof(double) * 4096)));
+    set = true;
+  }
   k_update_alpha<<<1, 256, 2 * sizeof(double) * k, s>>>(alpha, small, k, rho);
   KERNEL_CHECK();
 }

@@ -29,6 +29,10 @@ constexpr int kWWaves = kWThreads / 64;
 constexpr int kWRows = 512;             // max nnz of a document this kernel takes (LDS arrays)
 constexpr int kWChunk = 16;             // rows per Phase A reduce-scatter
 constexpr size_t kWLds = 160 * 1024;    // one workgroup per CU: all of the CU's LDS
+// fp32 k_estep_wide: a document with Σγ < k / kWThin shifts eθ by ψ(max γ) instead of ψ(Σγ).  Above it
+// max γ ≥ 1/kWThin, so the largest eθ' ≥ exp(ψ(1/48) − ψ(Σγ) − ψ(Σ_v λ_vt)) ≈ e^{−48.5 − 11.5 − 20.7} (Σγ ≤ 1e5,
+// colsum ≤ 1e9) = 9e-36, a normal float
+constexpr int kWThin = 48;
 
 template <typename T>
 struct WTr;
@@ -349,6 +353,7 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
   int it = 0;
   double b_tok = 0.0, c_tok = 0.0;
   const T kd = (T)k;
+  bool thin = false;  // fp32: the current eθ is shifted by ψ(max γ), bd[0][2] = ψ(Σγ) − ψ(max γ) (the γ update)
   while (true) {
     // Phase A: per-wave row sums of B_n·eθ, 16 rows at a time — register rows (compile-time indices;
     // their zero padding past nnz gives zero sums), then the LDS / streamed rows
@@ -402,7 +407,12 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
         T dot = sm.xs[0][n];
 #pragma unroll
         for (int w = 1; w < kWWaves; ++w) dot += sm.xs[w][n];
-        const T r = cts[j] * Tr::rcp(dot + eps[j]);
+        T e = eps[j];
+        if constexpr (sizeof(T) == 4) {  // eθ shifted by ψ(max γ): ε' carries e^{ψ(Σγ) − ψ(max γ)} (see the γ update)
+          if (thin)
+            e = fmin(fmax(__expf((T)(kLogEps - a.logscale[sm.ids[n]]) + (T)sm.bd[0][2]), Tr::eps_floor()), Tr::eps_cap());
+        }
+        const T r = cts[j] * Tr::rcp(dot + e);
         sm.rr[n] = r;
         rd = fma(r, dot, rd);
         if (BOUND && last) {
@@ -452,14 +462,52 @@ __global__ __launch_bounds__(kWThreads) void k_estep_wide(EStepArgs<T> a, int nl
     }
     // γ ← eθ ⊙ s + α ; eθ = exp(ψ(γ) − ψ(Σγ'))
     dg = T(0);
+    if constexpr (sizeof(T) == 8) {
 #pragma unroll
-    for (int q = 0; q < Q; ++q) {
-      if (t0 + q < k) {
-        const T gn = fma(eth[q], s[q], alp[q]);
-        dg += fabs(gn - gam[q]);
-        gam[q] = gn;
-        eth[q] = Tr::eth(gn, cs, pc[q]);
+      for (int q = 0; q < Q; ++q) {
+        if (t0 + q < k) {
+          const T gn = fma(eth[q], s[q], alp[q]);
+          dg += fabs(gn - gam[q]);
+          gam[q] = gn;
+          eth[q] = Tr::eth(gn, cs, pc[q]);
+        }
       }
+    } else {
+      T gmx = T(0);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        if (t0 + q < k) {
+          const T gn = fma(eth[q], s[q], alp[q]);
+          dg += fabs(gn - gam[q]);
+          gam[q] = gn;
+          gmx = fmax(gmx, gn);
+        }
+      }
+      // fp32, a thin document (Σγ' < k / kWThin): its mass over many topics leaves every γ_t small, and
+      // exp(ψ(γ_t) − ψ(Σγ')) flushes to zero for ALL of them (a 4-token document at k = 1024: γ_t ≈ 5/k,
+      // ψ ≈ −205) — dot = 0, γ = α from then on, where fp64 (and Spark) are still at e^{−205}.  The update is
+      // invariant to a common factor f of eθ once Spark's 1e-100 carries it too, so such a document takes
+      // ψ(max γ') for the shift (the workgroup and grid kernels' shift) and ε'_n·f with f = e^{ψ(Σγ') − ψ(max γ')}
+      // (clamped as ε'_n is: at its cap r = 0 and γ = α, which is what the 1e-100 does to such a document in
+      // Spark — a 4-token one at k = 2048).  One more barrier per iteration, block-uniform; ln f waits in
+      // bd[0][2] for the r lanes (after barrier (1)), so no register lives through Phase A for it.
+      // max γ' ≥ Σγ'/k, so elsewhere the largest eθ is above exp(ψ(1/kWThin) − ψ(Σγ')) · pc and nothing
+      // changes.  cs stays "what eθ was shifted by", which is all the bound's token terms ask of it.
+      thin = (as + sg) * T(kWThin) < kd;
+      if (thin) {
+        gmx = wave_max_dpp(gmx);
+        if (lane == 0) sm.bd[wave][1] = (double)gmx;  // (bd is otherwise the output phase's)
+        __syncthreads();
+        double m = sm.bd[0][1];
+#pragma unroll
+        for (int w = 1; w < kWWaves; ++w) m = fmax(m, sm.bd[w][1]);
+        const T cmax = Tr::psi((T)m);
+        if (tid == 0) sm.bd[0][2] = (double)(cs - cmax);
+        cs = cmax;
+      }
+#pragma unroll
+      for (int q = 0; q < Q; ++q)
+        if (t0 + q < k) eth[q] = Tr::eth(gam[q], cs, pc[q]);
     }
     ++it;
   }
