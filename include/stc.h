@@ -608,6 +608,39 @@ int stc_em_group_topic_assignments(stc_em_group* g, int64_t* indptr_out, int32_t
                              double doc_concentration, double topic_concentration, int state_dtype,
                              stc_em_group** out);
 
+/* ---- EM LDA, ranked queries ([U] DistributedLDAModel.describeTopics / topDocumentsPerTopic /
+ * topTopicsPerDocument) -----------------------------------------------------------------------
+ * Selections over the resident state (no copy of it, no full sort), of an STC_F64 or STC_F32 handle (the stored
+ * values widened; all arithmetic fp64).  Exact and bitwise reproducible: a result depends on the state alone.
+ * Tie rule: equal values rank by ascending index (term, document row, topic), whatever their number and
+ * wherever they lie.  Row sums Σ_j N_dk[d][j] are added sequentially in ascending j.
+ *   describe       per topic t the N = min(max_terms, V) terms with the largest N_wk[w][t] (ranked by the stored
+ *                  count, then normalised): idx_out int32[k×N], weight_out double[k×N] = N_wk[w][t] / N_k[t].
+ *                  Terms without a vertex (count 0) follow the others in ascending index.
+ *   top_documents  per topic t the documents with the largest N_dk[d][t] / Σ_j N_dk[d][j] (the count itself
+ *                  where the sum is 0), among the documents that have a vertex (at least one edge) only.
+ *                  cap = min(max_docs, D) is the stride of the outputs: row_out int64[k×cap] (corpus rows),
+ *                  weight_out double[k×cap]; *n_out = N = min(max_docs, document vertices), the first N of each
+ *                  topic's cap entries are written.
+ *   top_topics     per document the N = min(n_topics, k) topics with the largest N_dk[d][j]: idx_out int32[D×N],
+ *                  weight_out double[D×N] = N_dk[d][j] / Σ_j N_dk[d][j] (the count where the sum is 0: a document
+ *                  without a vertex yields topics 0 … N−1 with weight 0).
+ * The semantics are recalled from spark-mllib 2.4.3; Spark's own order among equal weights comes out of a
+ * BoundedPriorityQueue and argtopk and is not pinned by anything in the reference.
+ * Every call waits for queued iterations.  STC_ERR_INVALID_ARG: a NULL argument, a count <= 0; STC_ERR_STATE:
+ * no state yet, or (stc_em_*) a context connected to other ranks.
+ * Groups: describe runs on member 0 (N_wk, N_k are replicated); top_topics on every member over its rows;
+ * top_documents selects per member and merges the members' lists on the host by (weight descending, row
+ * ascending) — a weight depends on its own row only, so all three are bitwise the single handle's on the same
+ * state. */
+  int stc_em_describe(stc_em* em, int32_t max_terms, int32_t* idx_out, double* weight_out);
+  int stc_em_top_documents(stc_em* em, int64_t max_docs, int64_t* n_out, int64_t* row_out, double* weight_out);
+  int stc_em_top_topics(stc_em* em, int32_t n_topics, int32_t* idx_out, double* weight_out);
+  int stc_em_group_describe(stc_em_group* g, int32_t max_terms, int32_t* idx_out, double* weight_out);
+  int stc_em_group_top_documents(stc_em_group* g, int64_t max_docs, int64_t* n_out, int64_t* row_out,
+                                 double* weight_out);
+  int stc_em_group_top_topics(stc_em_group* g, int32_t n_topics, int32_t* idx_out, double* weight_out);
+
 #ifdef __cplusplus
 }
 #endif

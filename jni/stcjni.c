@@ -714,6 +714,72 @@ JNIEXPORT void JNICALL FN(emTopicAssignments)(JNIEnv* env, jclass c, jlong em, j
   check(env, st);
 }
 
+/* The ranked queries of a handle or a group: s = {k, nDocs, vocabSize, nEdges} of either.  A count <= 0 goes to the
+ * library with no array length to check (it refuses the count). */
+static int64_t at_most(int64_t n, int64_t hi) { return n < 0 ? 0 : (n < hi ? n : hi); }
+
+/* idx / weight: k × min(maxTerms, vocabSize) */
+static void em_describe_any(JNIEnv* env, const int64_t s[4], void* h, int group, jint max_terms, jintArray idx,
+                            jdoubleArray weight, const char* what) {
+  const int64_t n = s[0] * at_most(max_terms, s[2]);
+  if (NEED(idx, n, what) || NEED(weight, n, what)) return;
+  jint* ix = PIN(jint, Int, idx);
+  jdouble* w = PIN(jdouble, Double, weight);
+  int st = group ? stc_em_group_describe((stc_em_group*)h, max_terms, (int32_t*)ix, w)
+                 : stc_em_describe((stc_em*)h, max_terms, (int32_t*)ix, w);
+  UNPIN(Double, weight, w, 0);
+  UNPIN(Int, idx, ix, 0);
+  check(env, st);
+}
+/* rows / weight: k × min(maxDocs, nDocs); returns N, the valid entries at the head of each topic's range */
+static jlong em_top_documents_any(JNIEnv* env, const int64_t s[4], void* h, int group, jlong max_docs, jlongArray rows,
+                                  jdoubleArray weight, const char* what) {
+  const int64_t n = s[0] * at_most(max_docs, s[1]);
+  int64_t n_out = 0;
+  if (NEED(rows, n, what) || NEED(weight, n, what)) return 0;
+  jlong* r = PIN(jlong, Long, rows);
+  jdouble* w = PIN(jdouble, Double, weight);
+  int st = group ? stc_em_group_top_documents((stc_em_group*)h, max_docs, &n_out, (int64_t*)r, w)
+                 : stc_em_top_documents((stc_em*)h, max_docs, &n_out, (int64_t*)r, w);
+  UNPIN(Double, weight, w, 0);
+  UNPIN(Long, rows, r, 0);
+  return check(env, st) ? 0 : (jlong)n_out;
+}
+/* idx / weight: nDocs × min(nTopics, k) */
+static void em_top_topics_any(JNIEnv* env, const int64_t s[4], void* h, int group, jint n_topics, jintArray idx,
+                              jdoubleArray weight, const char* what) {
+  const int64_t n = s[1] * at_most(n_topics, s[0]);
+  if (NEED(idx, n, what) || NEED(weight, n, what)) return;
+  jint* ix = PIN(jint, Int, idx);
+  jdouble* w = PIN(jdouble, Double, weight);
+  int st = group ? stc_em_group_top_topics((stc_em_group*)h, n_topics, (int32_t*)ix, w)
+                 : stc_em_top_topics((stc_em*)h, n_topics, (int32_t*)ix, w);
+  UNPIN(Double, weight, w, 0);
+  UNPIN(Int, idx, ix, 0);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL FN(emDescribe)(JNIEnv* env, jclass c, jlong em, jint max_terms, jintArray idx,
+                                      jdoubleArray weight) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (em_shape(env, em, s)) return;
+  em_describe_any(env, s, EM(em), 0, max_terms, idx, weight, "emDescribe");
+}
+
+JNIEXPORT jlong JNICALL FN(emTopDocuments)(JNIEnv* env, jclass c, jlong em, jlong max_docs, jlongArray rows,
+                                           jdoubleArray weight) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (em_shape(env, em, s)) return 0;
+  return em_top_documents_any(env, s, EM(em), 0, max_docs, rows, weight, "emTopDocuments");
+}
+
+JNIEXPORT void JNICALL FN(emTopTopics)(JNIEnv* env, jclass c, jlong em, jint n_topics, jintArray idx,
+                                       jdoubleArray weight) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (em_shape(env, em, s)) return;
+  em_top_topics_any(env, s, EM(em), 0, n_topics, idx, weight, "emTopTopics");
+}
+
 /* ---- CountVectorizer (stc_cv_*: ml.feature.CountVectorizer / CountVectorizerModel) ---------------- */
 JNIEXPORT jlong JNICALL FN(cvFit)(JNIEnv* env, jclass c, jlong ctx, jbyteArray utf8, jlongArray tok_off,
                                   jlongArray doc_off, jlong vocab_size, jdouble min_df, jdouble max_df) {
@@ -1338,4 +1404,25 @@ JNIEXPORT void JNICALL FN(emGroupTopicAssignments)(JNIEnv* env, jclass c, jlong 
   UNPIN(Int, terms, te, 0);
   UNPIN(Long, indptr, ip, 0);
   check(env, st);
+}
+
+JNIEXPORT void JNICALL FN(emGroupDescribe)(JNIEnv* env, jclass c, jlong g, jint max_terms, jintArray idx,
+                                           jdoubleArray weight) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (emg_shape(env, g, s)) return;
+  em_describe_any(env, s, EMG(g), 1, max_terms, idx, weight, "emGroupDescribe");
+}
+
+JNIEXPORT jlong JNICALL FN(emGroupTopDocuments)(JNIEnv* env, jclass c, jlong g, jlong max_docs, jlongArray rows,
+                                                jdoubleArray weight) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (emg_shape(env, g, s)) return 0;
+  return em_top_documents_any(env, s, EMG(g), 1, max_docs, rows, weight, "emGroupTopDocuments");
+}
+
+JNIEXPORT void JNICALL FN(emGroupTopTopics)(JNIEnv* env, jclass c, jlong g, jint n_topics, jintArray idx,
+                                            jdoubleArray weight) {
+  int64_t s[4] = {0, 0, 0, 0};
+  if (emg_shape(env, g, s)) return;
+  em_top_topics_any(env, s, EMG(g), 1, n_topics, idx, weight, "emGroupTopTopics");
 }

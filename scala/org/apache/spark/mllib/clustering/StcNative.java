@@ -129,6 +129,14 @@ public final class StcNative {
   /** DistributedLDAModel.topicAssignments: per edge in CSR order the first topic with the largest factor; every
    *  array nullable: indptr nDocs + 1, terms nEdges (ascending per document), topics nEdges */
   public static native void emTopicAssignments(long em, long[] indptr, int[] terms, int[] topics);
+  /** DistributedLDAModel.describeTopics on the device: idx / weight k × min(maxTerms, vocabSize), per topic the
+   *  terms by (N_wk descending, term ascending), weight N_wk / N_k */
+  public static native void emDescribe(long em, int maxTerms, int[] idx, double[] weight);
+  /** topDocumentsPerTopic: rows / weight k × min(maxDocs, nDocs); returns N = min(maxDocs, document vertices), the
+   *  valid entries at the head of each topic's range, by (N_dk / row sum descending, row ascending) */
+  public static native long emTopDocuments(long em, long maxDocs, long[] rows, double[] weight);
+  /** topTopicsPerDocument: idx / weight nDocs × min(nTopics, k), by (N_dk descending, topic ascending) */
+  public static native void emTopTopics(long em, int nTopics, int[] idx, double[] weight);
 
   // ---- CountVectorizer (stc_cv_*: ml.feature.CountVectorizer / CountVectorizerModel; tokens as for HashingTF)
   /** fit: the vocabSize most frequent terms with minDf <= df <= maxDf (ties by the terms' UTF-8 bytes) */
@@ -252,4 +260,8 @@ public final class StcNative {
   public static native double[] emGroupLogLikelihood(long emGroup);
   /** every array nullable: indptr nDocs + 1, terms nEdges, topics nEdges, in the whole corpus's CSR order */
   public static native void emGroupTopicAssignments(long emGroup, long[] indptr, int[] terms, int[] topics);
+  /** emDescribe / emTopDocuments / emTopTopics over the whole corpus: bitwise a single handle's on the same state */
+  public static native void emGroupDescribe(long emGroup, int maxTerms, int[] idx, double[] weight);
+  public static native long emGroupTopDocuments(long emGroup, long maxDocs, long[] rows, double[] weight);
+  public static native void emGroupTopTopics(long emGroup, int nTopics, int[] idx, double[] weight);
 }

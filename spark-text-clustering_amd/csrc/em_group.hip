@@ -225,4 +225,71 @@ int stc_em_group_topic_assignments(stc_em_group* g, int64_t* indptr_out, int32_t
   });
 }
 
+// N_wk and N_k are replicated: member 0 answers
+int stc_em_group_describe(stc_em_group* g, int32_t max_terms, int32_t* idx_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(g, "em group");
+    STC_REQUIRE(idx_out && weight_out, "em: idx_out / weight_out");
+    STC_REQUIRE(max_terms > 0, "em: max_terms > 0");
+    require_usable(*g);
+    require_state(*g);
+    g->ctx[0]->use();
+    em::member_describe(*g->em[0], max_terms, idx_out, weight_out);
+  });
+}
+
+// every member selects its shard's best rows per topic; the global best N lie in the union of the shards' best
+// N, and a weight depends on its own row only: merged by (weight descending, row ascending) the answer is the
+// single handle's
+int stc_em_group_top_documents(stc_em_group* g, int64_t max_docs, int64_t* n_out, int64_t* row_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(g, "em group");
+    STC_REQUIRE(n_out && row_out && weight_out, "em: n_out / row_out / weight_out");
+    STC_REQUIRE(max_docs > 0, "em: max_docs > 0");
+    require_usable(*g);
+    require_state(*g);
+    const size_t n = (size_t)g->n();
+    std::vector<std::vector<int64_t>> rows(n);
+    std::vector<std::vector<double>> w(n);
+    std::vector<int64_t> ni(n, 0);
+    for_members(*g, [&](int i) {
+      ni[(size_t)i] = em::member_top_documents(*g->em[(size_t)i], max_docs, g->row0[(size_t)i], rows[(size_t)i], w[(size_t)i]);
+    });
+    int64_t vertices = 0;
+    for (size_t i = 0; i < n; ++i) vertices += ni[i];
+    const int64_t N = std::min(max_docs, vertices), cap = std::min(max_docs, g->D);
+    std::vector<std::pair<double, int64_t>> all;
+    for (int t = 0; t < g->k; ++t) {
+      all.clear();
+      for (size_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < ni[i]; ++j) all.emplace_back(w[i][(size_t)(t * ni[i] + j)], rows[i][(size_t)(t * ni[i] + j)]);
+      std::sort(all.begin(), all.end(), [](const std::pair<double, int64_t>& a, const std::pair<double, int64_t>& b) {
+        return a.first > b.first || (a.first == b.first && a.second < b.second);
+      });
+      for (int64_t j = 0; j < N; ++j) {
+        row_out[t * cap + j] = all[(size_t)j].second;
+        weight_out[t * cap + j] = all[(size_t)j].first;
+      }
+    }
+    *n_out = N;
+  });
+}
+
+// every member ranks its own rows; concatenated in row order
+int stc_em_group_top_topics(stc_em_group* g, int32_t n_topics, int32_t* idx_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(g, "em group");
+    STC_REQUIRE((idx_out && weight_out) || g->D == 0, "em: idx_out / weight_out");
+    STC_REQUIRE(n_topics > 0, "em: n_topics > 0");
+    require_usable(*g);
+    require_state(*g);
+    const int64_t N = std::min<int64_t>(n_topics, g->k);
+    for_members(*g, [&](int i) {
+      const int64_t off = g->row0[(size_t)i] * N;
+      em::member_top_topics(*g->em[(size_t)i], n_topics, idx_out ? idx_out + off : nullptr,
+                            weight_out ? weight_out + off : nullptr);
+    });
+  });
+}
+
 }  // extern "C"

@@ -7,6 +7,8 @@
 // stc_em_get_state serve a member.
 #pragma once
 
+#include <vector>
+
 #include "stc_handles.h"
 
 struct stc_em;
@@ -29,6 +31,13 @@ void member_next(stc_em& m, int32_t n_iterations);  // collective
 void member_log_likelihood(stc_em& m, double* ll, double* term_prior, double* doc_prior);
 // the member's rows: indptr_out int64[D_i + 1] from 0, terms_out / topics_out int32[E_i]
 void member_topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out);
+// the ranked queries (stc.h) over the member's rows and its replica of N_wk / N_k; none is collective.
+// top_documents: per topic the member's best N_i = min(max_docs, its document vertices) rows, as global rows
+// (row0 + local row): rows / weights k×N_i; returns N_i
+void member_describe(stc_em& m, int32_t max_terms, int32_t* idx_out, double* weight_out);
+int64_t member_top_documents(stc_em& m, int64_t max_docs, int64_t row0, std::vector<int64_t>& rows,
+                             std::vector<double>& weights);
+void member_top_topics(stc_em& m, int32_t n_topics, int32_t* idx_out, double* weight_out);
 void member_wait(stc_em& m);  // until the member's queued iterations have finished
 
 }  // namespace em

@@ -27,12 +27,16 @@
 // templates on that type; a load widens to double, a store of a new element rounds it once, and everything
 // else — counts, α, η, N_k, inv, γ, accumulators, partials, the scalars — is fp64 in the same order in both
 // instantiations.  N_k is the fp64 column sum of the stored N_wk.
+//
+// Ranked queries (describe, top_documents, top_topics): selections over the resident state by em_rank.hip's
+// kernels; this file sizes their scratch, feeds them the state's buffers and copies the lists out.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <vector>
 
 #include "collectives.h"
+#include "em_rank.h"
 #include "lda_em.h"
 #include "stc_handles.h"
 
@@ -491,6 +495,8 @@ struct stc_em {
   bool member = false;
   int64_t pos_base = 0;  // edges in the earlier shards
   DevBuf gdeg;           // int64[V]: every term's edges over all members (empty: the local graph is the whole one)
+  rank::Scratch rk;      // the ranked queries' scratch (em_rank.h; allocated by their first call)
+  int64_t doc_vertices = -1;  // the documents with an edge (counted by the first top_documents)
 };
 
 namespace stc {
@@ -876,6 +882,86 @@ void topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32
   wait_stream(*m.ctx, s);
 }
 
+// ---- ranked queries (em_rank.h) ----------------------------------------------------------------------
+bool is_f32(const stc_em& m) { return m.dtype == STC_F32; }
+
+// describeTopics: per topic the N = min(max_terms, V) largest N_wk[w][t], (count descending, term ascending),
+// weights N_wk[w][t] / N_k[t]
+void describe(stc_em& m, int32_t max_terms, int32_t* idx_out, double* weight_out, bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
+  STC_REQUIRE(idx_out && weight_out, "em: idx_out / weight_out");
+  STC_REQUIRE(max_terms > 0, "em: max_terms > 0");
+  require_state(m);
+  m.ctx->use();
+  hipStream_t s = m.ctx->stream;
+  const int64_t N = std::min<int64_t>(max_terms, m.V), total = N * m.k;
+  m.rk.out_row.reserve(8 * total);
+  m.rk.out_w.reserve(8 * total);
+  rank::select_columns(s, m.rk, m.nwk[m.cur].p, is_f32(m), m.V, m.k, N, nullptr, m.nk.as<double>(), 0,
+                       m.rk.out_row.as<int64_t>(), m.rk.out_w.as<double>());
+  std::vector<int64_t> rows((size_t)total);
+  HIP_CHECK(hipMemcpyAsync(rows.data(), m.rk.out_row.p, 8 * total, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(weight_out, m.rk.out_w.p, 8 * total, hipMemcpyDeviceToHost, s));
+  wait_stream(*m.ctx, s);
+  std::copy(rows.begin(), rows.end(), idx_out);
+}
+
+// topDocumentsPerTopic over this handle's rows: N = min(max_docs, its document vertices) per topic, rows[t·N + i]
+// = row0 + row, by (N_dk[d][t] / Σ_j N_dk[d][j] descending, row ascending); returns N
+int64_t top_documents(stc_em& m, int64_t max_docs, int64_t row0, std::vector<int64_t>& rows, std::vector<double>& w,
+                      bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
+  STC_REQUIRE(max_docs > 0, "em: max_docs > 0");
+  require_state(m);
+  m.ctx->use();
+  hipStream_t s = m.ctx->stream;
+  if (m.doc_vertices < 0) {
+    m.rk.count.reserve(8);
+    rank::count_vertices(s, m.rows.ptr.as<int64_t>(), m.D, m.rk.count.as<int64_t>());
+    int64_t n = 0;
+    HIP_CHECK(hipMemcpyAsync(&n, m.rk.count.p, 8, hipMemcpyDeviceToHost, s));
+    wait_stream(*m.ctx, s);
+    m.doc_vertices = n;
+  }
+  const int64_t N = std::min(max_docs, m.doc_vertices), total = N * m.k;
+  rows.assign((size_t)total, 0);
+  w.assign((size_t)total, 0.0);
+  if (N == 0) return 0;
+  m.rk.rowsum.reserve(8 * m.D);
+  m.rk.out_row.reserve(8 * total);
+  m.rk.out_w.reserve(8 * total);
+  rank::row_sums(s, m.ndk[m.cur].p, is_f32(m), m.rows.ptr.as<int64_t>(), m.D, m.k, m.rk.rowsum.as<double>());
+  rank::select_columns(s, m.rk, m.ndk[m.cur].p, is_f32(m), m.D, m.k, N, m.rk.rowsum.as<double>(), nullptr, row0,
+                       m.rk.out_row.as<int64_t>(), m.rk.out_w.as<double>());
+  HIP_CHECK(hipMemcpyAsync(rows.data(), m.rk.out_row.p, 8 * total, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(w.data(), m.rk.out_w.p, 8 * total, hipMemcpyDeviceToHost, s));
+  wait_stream(*m.ctx, s);
+  return N;
+}
+
+// topTopicsPerDocument: per row the N = min(n_topics, k) largest N_dk[d][j], (count descending, topic ascending),
+// weights N_dk[d][j] / Σ_j N_dk[d][j] (a row whose sum is 0, as a document without a vertex: 0 … N−1, weight 0)
+void top_topics(stc_em& m, int32_t n_topics, int32_t* idx_out, double* weight_out, bool as_member = false) {
+  require_idle_single(*m.ctx, as_member);
+  STC_REQUIRE((idx_out && weight_out) || m.D == 0, "em: idx_out / weight_out");
+  STC_REQUIRE(n_topics > 0, "em: n_topics > 0");
+  require_state(m);
+  if (m.D == 0) return;
+  m.ctx->use();
+  hipStream_t s = m.ctx->stream;
+  const int N = std::min<int>(n_topics, m.k);
+  const int64_t total = m.D * N;
+  m.rk.rowsum.reserve(8 * m.D);
+  m.rk.out_row.reserve(4 * total);
+  m.rk.out_w.reserve(8 * total);
+  rank::row_sums(s, m.ndk[m.cur].p, is_f32(m), nullptr, m.D, m.k, m.rk.rowsum.as<double>());
+  rank::select_rows(s, m.ndk[m.cur].p, is_f32(m), m.rk.rowsum.as<double>(), m.D, m.k, N, m.rk.out_row.as<int32_t>(),
+                    m.rk.out_w.as<double>());
+  HIP_CHECK(hipMemcpyAsync(idx_out, m.rk.out_row.p, 4 * total, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(weight_out, m.rk.out_w.p, 8 * total, hipMemcpyDeviceToHost, s));
+  wait_stream(*m.ctx, s);
+}
+
 void shape(const stc_em& m, int32_t* k, int64_t* n_docs, int64_t* vocab, int64_t* n_edges) {
   if (k) *k = m.k;
   if (n_docs) *n_docs = m.D;
@@ -904,6 +990,16 @@ void member_log_likelihood(stc_em& m, double* ll, double* term_prior, double* do
 }
 void member_topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32_t* topics_out) {
   topic_assignments(m, indptr_out, terms_out, topics_out, true);
+}
+void member_describe(stc_em& m, int32_t max_terms, int32_t* idx_out, double* weight_out) {
+  describe(m, max_terms, idx_out, weight_out, true);
+}
+int64_t member_top_documents(stc_em& m, int64_t max_docs, int64_t row0, std::vector<int64_t>& rows,
+                             std::vector<double>& weights) {
+  return top_documents(m, max_docs, row0, rows, weights, true);
+}
+void member_top_topics(stc_em& m, int32_t n_topics, int32_t* idx_out, double* weight_out) {
+  top_topics(m, n_topics, idx_out, weight_out, true);
 }
 void member_wait(stc_em& m) {
   m.ctx->use();
@@ -990,6 +1086,35 @@ int stc_em_topic_assignments(stc_em* m, int64_t* indptr_out, int32_t* terms_out,
   return guard([&] {
     STC_REQUIRE(m, "em");
     em::topic_assignments(*m, indptr_out, terms_out, topics_out);
+  });
+}
+
+int stc_em_describe(stc_em* m, int32_t max_terms, int32_t* idx_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::describe(*m, max_terms, idx_out, weight_out);
+  });
+}
+
+int stc_em_top_documents(stc_em* m, int64_t max_docs, int64_t* n_out, int64_t* row_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    STC_REQUIRE(n_out && row_out && weight_out, "em: n_out / row_out / weight_out");
+    std::vector<int64_t> rows;
+    std::vector<double> w;
+    const int64_t N = em::top_documents(*m, max_docs, 0, rows, w), cap = std::min(max_docs, m->D);
+    for (int t = 0; t < m->k; ++t) {
+      std::copy(rows.begin() + t * N, rows.begin() + (t + 1) * N, row_out + t * cap);
+      std::copy(w.begin() + t * N, w.begin() + (t + 1) * N, weight_out + t * cap);
+    }
+    *n_out = N;
+  });
+}
+
+int stc_em_top_topics(stc_em* m, int32_t n_topics, int32_t* idx_out, double* weight_out) {
+  return guard([&] {
+    STC_REQUIRE(m, "em");
+    em::top_topics(*m, n_topics, idx_out, weight_out);
   });
 }
 

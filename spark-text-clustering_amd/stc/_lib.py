@@ -191,6 +191,12 @@ SIGNATURES = {
     "stc_em_group_synchronize": (_int, [_p]),
     "stc_em_group_log_likelihood": (_int, [_p, _pdbl, _pdbl]),
     "stc_em_group_topic_assignments": (_int, [_p, _pi64, _pi32, _pi32]),
+    "stc_em_describe": (_int, [_p, _i32, _pi32, _pdbl]),
+    "stc_em_top_documents": (_int, [_p, _i64, _pi64, _pi64, _pdbl]),
+    "stc_em_top_topics": (_int, [_p, _i32, _pi32, _pdbl]),
+    "stc_em_group_describe": (_int, [_p, _i32, _pi32, _pdbl]),
+    "stc_em_group_top_documents": (_int, [_p, _i64, _pi64, _pi64, _pdbl]),
+    "stc_em_group_top_topics": (_int, [_p, _i32, _pi32, _pdbl]),
 }
 
 

@@ -377,12 +377,55 @@ def _em_state_dtype(lib, em_handle):
     return {L.STC_F64: "f64", L.STC_F32: "f32"}[t.value]
 
 
-class EmHandle:
+class _EmRanked:
+    """The ranked queries of an ``EmHandle`` (``_rank = "stc_em_"``) or ``EmGroup`` (``"stc_em_group_"``): device
+    selections over the resident state, ties by ascending index (include/stc.h, "EM LDA, ranked queries")."""
+
+    def _rank_call(self, name):
+        return getattr(self._rank_lib(), self._rank + name)
+
+    def describe(self, max_terms=10):
+        """(terms int32[k×N], weights float64[k×N]), N = min(max_terms, V): per topic the terms with the largest
+        N_wk[w][t], (count descending, term ascending), weights N_wk[w][t] / N_k[t]"""
+        n = max(0, min(int(max_terms), self.vocab_size))
+        idx = np.zeros((self.k, n), np.int32)
+        w = np.zeros((self.k, n), np.float64)
+        L.check(self._rank_call("describe")(self.handle, int(max_terms), L.ptr(idx, C.c_int32), L.ptr(w, C.c_double)))
+        return idx, w
+
+    def top_documents(self, max_docs):
+        """(rows int64[k×N], weights float64[k×N]), N = min(max_docs, documents with an edge): per topic the corpus
+        rows with the largest N_dk[d][t] / Σ_j N_dk[d][j], (weight descending, row ascending)"""
+        cap = max(0, min(int(max_docs), self.num_docs))
+        rows = np.zeros((self.k, cap), np.int64)
+        w = np.zeros((self.k, cap), np.float64)
+        n = C.c_int64()
+        L.check(self._rank_call("top_documents")(self.handle, int(max_docs), C.byref(n), L.ptr(rows, C.c_int64),
+                                                 L.ptr(w, C.c_double)))
+        return rows[:, :n.value].copy(), w[:, :n.value].copy()
+
+    def top_topics(self, n_topics):
+        """(topics int32[D×N], weights float64[D×N]), N = min(n_topics, k): per document the topics with the largest
+        N_dk[d][j], (count descending, topic ascending), weights N_dk[d][j] / Σ_j N_dk[d][j]; a document without an
+        edge: topics 0 … N−1 with weight 0"""
+        n = max(0, min(int(n_topics), self.k))
+        idx = np.zeros((self.num_docs, n), np.int32)
+        w = np.zeros((self.num_docs, n), np.float64)
+        L.check(self._rank_call("top_topics")(self.handle, int(n_topics), L.ptr(idx, C.c_int32), L.ptr(w, C.c_double)))
+        return idx, w
+
+
+class EmHandle(_EmRanked):
     """Owns one stc_em: the EM optimizer's bipartite graph (built once from ``corpus``, which may be freed
     afterwards) and its state N_dk (D×k), N_wk (V×k), N_k on the GPU.  ``doc_concentration`` /
     ``topic_concentration``: −1 picks Spark's EM defaults 50/k + 1 and 1.1, anything else must be > 1.
     ``dtype``: "f64", or "f32" — N_dk and N_wk stored as fp32 (every new element rounded once, when stored),
     all arithmetic, N_k and the scores in fp64; the corpus stays STC_F64 and the state travels as float64."""
+
+    _rank = "stc_em_"
+
+    def _rank_lib(self):
+        return self.ctx.lib
 
     def __init__(self, ctx: Context, corpus: DeviceCsr, k, doc_concentration=-1.0, topic_concentration=-1.0,
                  dtype="f64"):
@@ -455,13 +498,18 @@ class EmHandle:
             pass
 
 
-class EmGroup:
+class EmGroup(_EmRanked):
     """Owns one stc_em_group: the EM optimizer over several devices from ONE process.  The host ``corpus`` is
     sharded by the library (contiguous document ranges balanced by entries; document ids stay global); N_dk is
     kept by the member that owns the document, N_wk and N_k are replicated and all-reduced once per iteration.
     ``devices`` repeating one device runs that decomposition on the one device.  ``EmHandle``'s methods and
     attributes, over the whole corpus.  ``dtype`` "f32": every member stores its state as fp32 (``EmHandle``) and
     N_wk' is all-reduced as fp32."""
+
+    _rank = "stc_em_group_"
+
+    def _rank_lib(self):
+        return self.lib
 
     def __init__(self, devices, corpus: CsrMatrix, k, doc_concentration=-1.0, topic_concentration=-1.0, dtype="f64"):
         self.handle = None
@@ -738,15 +786,28 @@ class DistributedLDAModel:
         dt = self._d["doc_topics"]
         return self._d["doc_ids"].copy(), dt / dt.sum(axis=1, keepdims=True)
 
-    def topTopicsPerDocument(self, k):
-        """[(document id, topic indices, topic weights)], each document's top k topics by weight descending"""
+    def topTopicsPerDocument(self, k, device=False, ctx: Context | None = None):
+        """[(document id, topic indices, topic weights)], each document's top k topics by weight descending.
+        ``device=True``: a selection on the model's EM graph on the GPU (``EmHandle.top_topics``: ranked by the
+        count, ties to the smaller topic) instead of a sort of the host copy"""
+        if device:
+            idx, w = self._em_handle(ctx).top_topics(k)
+            ids = self._d["doc_ids"]
+            rows = ids if self._em_rows_are_ids else np.arange(ids.size)
+            return [(int(d), idx[r].astype(np.int64), w[r]) for d, r in zip(ids, rows)]
         ids, td = self.topicDistributions()
         n = min(int(k), self.k)
         top = np.argsort(-td, axis=1, kind="stable")[:, :n]
         return [(int(ids[i]), top[i], td[i, top[i]]) for i in range(ids.size)]
 
-    def topDocumentsPerTopic(self, maxDocumentsPerTopic):
-        """[(document ids, weights)] per topic: the documents with the largest weight of it, descending"""
+    def topDocumentsPerTopic(self, maxDocumentsPerTopic, device=False, ctx: Context | None = None):
+        """[(document ids, weights)] per topic: the documents with the largest weight of it, descending.
+        ``device=True``: a selection on the model's EM graph on the GPU (``EmHandle.top_documents``: ties to the
+        smaller row, which is the smaller document id) instead of k sorts of the host copy"""
+        if device:
+            rows, w = self._em_handle(ctx).top_documents(maxDocumentsPerTopic)
+            ids = rows if self._em_rows_are_ids else self._d["doc_ids"][rows]
+            return [(ids[t].astype(self._d["doc_ids"].dtype), w[t]) for t in range(self.k)]
         ids, td = self.topicDistributions()
         n = min(int(maxDocumentsPerTopic), ids.size)
         out = []
@@ -785,8 +846,13 @@ class DistributedLDAModel:
                                                     gamma_shape=self.gammaShape, seed=seed, dtype=dtype, ctx=ctx)
         return self._local[key]
 
-    def describeTopics(self, maxTermsPerTopic=10, ctx: Context | None = None):
-        """Top terms per topic by n_wk / Σ_w n_wk (the EM model's column totals), on the GPU."""
+    def describeTopics(self, maxTermsPerTopic=10, ctx: Context | None = None, device=False):
+        """Top terms per topic by n_wk / Σ_w n_wk (the EM model's column totals), on the GPU.
+        ``device=True``: a selection over the N_wk of the model's EM graph (``EmHandle.describe``) instead of an
+        upload into a local model and its full sort"""
+        if device:
+            idx, w = self._em_handle(ctx).describe(maxTermsPerTopic)
+            return [(t, idx[t].astype(np.int64), w[t]) for t in range(self.k)]
         return self.toLocal(ctx=ctx).describeTopics(maxTermsPerTopic)
 
 

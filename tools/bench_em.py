@@ -21,6 +21,12 @@ copied out) is timed in the same run under the same discipline, from the state t
 term index, one gathered k-row and the 4 B result per edge: E·(8 + 8k), at --dtype f32 E·(8 + 4k).  The row pass it is to be read
 against is one kernel of the iteration; its time comes from a kernel trace of this tool's run.
 
+The ranked queries ("ranked" in the line; --no-ranked skips them): describe(10), describe(300), top_documents(10)
+and top_topics(1) from the state the timed iterations left, each warm (one untimed call) as the median of
+--repeats calls that end in the copy to the host — on the device selection (csrc/em_rank.hip) and, in the same
+run, the way the question was answered before it: toLocal().describeTopics (the upload into an online handle
+untimed, reported as to_local_ms) and a download of N_dk plus NumPy.  floor_bytes is one read of the matrix.
+
 --devices 0,0 or 0,1,… runs the same cases through an EmGroup (stc_em_group: documents sharded over the members,
 one all-reduce of N_wk' per iteration) and reports the same lines, with "devices" and "transport" added.  A
 repeated device shows the decomposition's overhead on one GPU only: the in-process transport synchronises the
@@ -102,7 +108,59 @@ def assign_pass_ms(ctx, h, sync, iters, warmup, repeats):
     return ms
 
 
-def measure(ctx, h, sync, info, iters, warmup, repeats):
+def median_ms(f, repeats):
+    """median and spread of `repeats` timed calls of f() after one untimed call (every f ends in a copy to the host)"""
+    f()
+    ms = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        f()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return {"ms": float(np.median(ms)), "min": float(min(ms)), "max": float(max(ms))}
+
+
+def ranked_queries(stc, ctx, h, repeats):
+    """describe(10), describe(300), top_documents(10), top_topics(1): the device selection (stc_em_describe, …)
+    against the way the same question was answered before it — toLocal().describeTopics (the V×k counts uploaded
+    into an online LdaHandle once, untimed; each call its full segmented sort), and a download of N_dk plus NumPy
+    (normalise, then a stable argsort per topic / per row).  floor_bytes: one read of the matrix, R·k·sizeof(T)."""
+    elem = 4 if getattr(h, "dtype", "f64") == "f32" else 8
+    out = {}
+    local = None
+    try:
+        _, nwk, _ = h.state()
+        alpha, eta = h.concentrations()
+        t0 = time.perf_counter()
+        local = stc.LDAModel.from_topics(nwk, np.full(h.k, alpha), eta, ctx=ctx)
+        out["to_local_ms"] = (time.perf_counter() - t0) * 1e3
+    except stc.StcError as e:  # a term without an edge has a 0 row, which the online handle refuses
+        out["to_local_error"] = str(e)
+
+    def host_top_documents(n):
+        dt = h.state()[0]
+        td = dt / dt.sum(axis=1, keepdims=True)
+        return [np.argsort(-td[:, t], kind="stable")[:n] for t in range(h.k)]
+
+    def host_top_topics(n):
+        dt = h.state()[0]
+        td = dt / dt.sum(axis=1, keepdims=True)
+        return np.argsort(-td, axis=1, kind="stable")[:, :n]
+
+    for name, n, dev, host, rows in (
+            ("describe_10", 10, h.describe, local and local.describeTopics, h.vocab_size),
+            ("describe_300", 300, h.describe, local and local.describeTopics, h.vocab_size),
+            ("top_documents_10", 10, h.top_documents, host_top_documents, h.num_docs),
+            ("top_topics_1", 1, h.top_topics, host_top_topics, h.num_docs)):
+        r = {"device": median_ms(lambda: dev(n), repeats), "floor_bytes": rows * h.k * elem}
+        if host:
+            r["host"] = median_ms(lambda: host(n), repeats)
+        out[name] = r
+    if local:
+        local._h.close()
+    return out
+
+
+def measure(stc, ctx, h, sync, info, iters, warmup, repeats, ranked):
     h.next(warmup)
     sync()
     ms = []
@@ -128,6 +186,8 @@ def measure(ctx, h, sync, info, iters, warmup, repeats):
                assign_algorithmic_bytes_per_s=E * (8.0 + row) / (amed * 1e-3))
     if "reference_s_per_iteration" in info:
         out["speedup_vs_reference"] = info["reference_s_per_iteration"] / (med * 1e-3)
+    if ranked:
+        out["ranked"] = ranked_queries(stc, ctx, h, repeats)
     return out
 
 
@@ -147,6 +207,8 @@ def main():
                    help="comma-separated device ids of an EmGroup (0,0: two members on device 0); empty: one EmHandle")
     p.add_argument("--dtype", choices=("f64", "f32"), default="f64",
                    help="how the handle or group stores N_dk / N_wk (f32: rounded when stored; arithmetic stays fp64)")
+    p.add_argument("--no-ranked", action="store_true",
+                   help="skip the ranked queries (describe, top_documents, top_topics: device against the host's way)")
     a = p.parse_args()
     import stc
 
@@ -155,7 +217,7 @@ def main():
     for case in (("golden", "zipf") if a.case == "all" else (a.case,)):
         h, sync, info = (golden_case(stc, ctx, devices, a.dtype) if case == "golden" else
                          zipf_case(stc, ctx, devices, a.docs, a.tokens, a.vocab, a.k, a.workers, a.dtype))
-        print(json.dumps(measure(ctx, h, sync, info, a.iters, a.warmup, a.repeats)), flush=True)
+        print(json.dumps(measure(stc, ctx, h, sync, info, a.iters, a.warmup, a.repeats, not a.no_ranked)), flush=True)
         h.close()
 
 
