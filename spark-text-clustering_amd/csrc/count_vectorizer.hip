@@ -15,7 +15,8 @@
 //           short term needs no second read; an insert that meets its own string reports a duplicate (the
 //           smallest index, whatever the order).
 // transform per-token lookup (hash, probe, byte compare) → the indices of every document sorted (one wave per
-//           document, a bitonic network in registers; hipcub's segmented radix sort past 1024 tokens) → run
+//           document, wave_sort.h's bitonic network in registers; past 1024 tokens hipcub's segmented radix sort,
+//           the hashing::sort_long_docs that HashingTF uses) → run
 //           heads and lengths by flat scans → minTF filter → CSR.  No atomics on the CSR, no per-document
 //           counters: a run of 2^31−1 equal tokens is one subtraction.
 // Integer atomics only, and only where the order cannot show (a kept-term count, the CAS inserts, a min).
@@ -27,6 +28,7 @@
 
 #include "collectives.h"
 #include "stc_handles.h"
+#include "wave_sort.h"
 
 // CountVectorizerModel: term j is blob[term_off[j] .. term_off[j+1]), index = position
 struct stc_cvm {
@@ -426,55 +428,8 @@ void lookup(Ctx& c, const stc_cvm& m, const TokView& tk, int32_t oov, int32_t* d
 // ---------------------------------------------------------------------------------------
 // transform: the sorted indices of every document → runs → CSR
 // ---------------------------------------------------------------------------------------
-// the indices of one document sorted in registers: a bitonic network over 64·P keys, P per lane (element
-// lane·P + p in register p; partners at distance ≥ P across lanes, below P inside the lane), the structure
-// of hashing_tf.hip's sort.  Documents past kSortCap tokens go to hipcub's segmented radix sort.
-constexpr int kSortCap = 1024;  // ≤ 16 keys per lane
-constexpr int kDocWaves = 4;    // documents in flight per workgroup (one per wave)
-
-// x from lane ^ lx: DPP where a pattern exists (xor 1 / 2 quad_perm, xor 4 = half-row mirror after quad_perm
-// xor 3, xor 8 = row rotate by 8), ds_swizzle for xor 16, ds_bpermute for xor 32
-__device__ __forceinline__ int32_t shfl_xor_dpp(int32_t v, int lx) {
-  switch (lx) {
-    case 1: return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    case 2: return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    case 4: return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x1B, 0xF, 0xF, false),  // [3,2,1,0]
-                                            0x141, 0xF, 0xF, false);     // row_half_mirror
-    case 8: return __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);  // row_ror:8
-    case 16: return __builtin_amdgcn_ds_swizzle(v, 0x401F);              // and 0x1F, xor 0x10
-    default: return __shfl_xor(v, lx, 64);
-  }
-}
-template <int P>
-__device__ __forceinline__ void bitonic_regs(int32_t (&x)[P], int lane) {
-  constexpr int m = 64 * P;  // fully unrolled: every partner distance is a constant
-#pragma unroll
-  for (int k = 2; k <= m; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (j >= P) {  // partner in lane ^ (j / P), same register
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          const int e = lane * P + p;
-          const int32_t o = shfl_xor_dpp(x[p], j / P);
-          const bool lower = (e & j) == 0, asc = (e & k) == 0;
-          x[p] = (lower == asc) ? min(x[p], o) : max(x[p], o);
-        }
-      } else {
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          const int q = p ^ j;
-          if (q > p) {
-            const bool asc = ((lane * P + p) & k) == 0;
-            const int32_t a = x[p], b = x[q];
-            x[p] = asc ? min(a, b) : max(a, b);
-            x[q] = asc ? max(a, b) : min(a, b);
-          }
-        }
-      }
-    }
-  }
-}
+// the indices of one document sorted in registers by wave_sort.h's bitonic network (the one HashingTF uses);
+// documents past kSortCap tokens go to hipcub's segmented radix sort (hashing::sort_long_docs)
 template <int P>
 __device__ __forceinline__ void sort_doc(const int32_t* __restrict__ keys, int32_t* __restrict__ sorted, int64_t s,
                                          int n, int lane) {
@@ -508,20 +463,7 @@ __global__ __launch_bounds__(64 * kDocWaves) void k_tf_sort_docs(const int32_t* 
     }
     const int n = (int)n64;
     if (n == 0) continue;
-    if (n <= 64) sort_doc<1>(keys, sorted, s, n, lane);
-    else if (n <= 128) sort_doc<2>(keys, sorted, s, n, lane);
-    else if (n <= 256) sort_doc<4>(keys, sorted, s, n, lane);
-    else if (n <= 512) sort_doc<8>(keys, sorted, s, n, lane);
-    else sort_doc<16>(keys, sorted, s, n, lane);
-  }
-}
-__global__ __launch_bounds__(256) void k_tf_large_segments(const int32_t* __restrict__ large, int32_t n_large,
-                                                           const int64_t* __restrict__ doc_off,
-                                                           int64_t* __restrict__ beg, int64_t* __restrict__ end) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n_large) {
-    beg[i] = doc_off[large[i]];
-    end[i] = doc_off[large[i] + 1];
+    with_keys_per_lane<1, kSortCap / 64>(n, [&](auto pc) { sort_doc<decltype(pc)::value>(keys, sorted, s, n, lane); });
   }
 }
 
@@ -795,17 +737,7 @@ void transform(Ctx& c, const stc_cvm& m, const TokView& tk, double min_tf, int b
     HIP_CHECK(hipStreamSynchronize(st));
   }
   if (n_large > 0) {  // long documents: hipcub's segmented radix sort
-    DevBuf& seg = c.scratch[3];
-    seg.reserve(sizeof(int64_t) * 2 * n_large);
-    int64_t* beg = seg.as<int64_t>();
-    int64_t* end = beg + n_large;
-    k_tf_large_segments<<<(unsigned)ceil_div(n_large, 256), 256, 0, st>>>(large, n_large, tk.doc_off, beg, end);
-    KERNEL_CHECK();
-    int nbits = 1;
-    while ((int64_t(1) << nbits) <= m.n_terms) ++nbits;
-    with_temp(tmp, [&](void* t, size_t& tb) {
-      return hipcub::DeviceSegmentedRadixSort::SortKeys(t, tb, k, k2, (int)n, n_large, beg, end, 0, nbits, st);
-    });
+    hashing::sort_long_docs(c, k, k2, n, large, n_large, tk.doc_off, oov /* the largest key */, c.scratch[3], tmp);
   }
   HIP_CHECK(hipMemsetAsync(rid, 0, 4 * n, st));
   k_tf_doc_starts<<<grid_for(n_docs), 256, 0, st>>>(tk.doc_off, n_docs, rid);

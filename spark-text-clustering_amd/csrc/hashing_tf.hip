@@ -6,15 +6,18 @@
 //
 // Layout: the corpus arrives as ONE UTF-8 byte blob + int64 token offsets + int64 doc offsets
 // (plain arrays a JNI caller can hand over without per-string objects).  One wave per document hashes
-// its tokens (K1, aligned dword reads) straight into registers and sorts them there (K2 pass A; hipcub's
-// segmented sort only for documents past 1024 tokens, hashed to memory first); pass B emits the sorted
-// distinct ids + run lengths — no atomics on the CSR, so hot terms ("the") cost nothing extra.
+// its tokens (K1, aligned dword reads) straight into registers and sorts them there (K2 pass A; the register
+// sort is wave_sort.h's; hipcub's segmented sort only for documents past 1024 tokens, hashed to memory
+// first — sort_long_docs, which CountVectorizer's transform shares); pass B emits the sorted
+// distinct ids + run lengths — no atomics on the CSR, so hot terms ("the") cost nothing extra.  A corpus whose
+// documents all hold ≤ 256 tokens takes one look-back pass instead (k_doc_hash_emit; STC_TF_MODE=0: the passes).
 #include <hipcub/hipcub.hpp>
 
 #include <map>
 #include <mutex>
 
-#include "stc_internal.h"
+#include "stc_handles.h"
+#include "wave_sort.h"
 
 namespace stc {
 namespace hashing {
@@ -102,13 +105,13 @@ __device__ __forceinline__ int32_t murmur3(const uint8_t* p, uint32_t n) {
 // four tokens per thread and step, a grid stride apart (neighbouring lanes keep neighbouring tokens,
 // so the byte loads stay coalesced) — four independent offset → window → hash chains in flight, every
 // window issued before the first hash
-template <bool SPARK24, typename O>
+template <bool SPARK24>
 __global__ __launch_bounds__(256) void k_hash(const uint8_t* __restrict__ utf8,
-                                              const O* __restrict__ tok_off, int64_t n_tok,
+                                              const int64_t* __restrict__ tok_off, int64_t n_tok,
                                               int32_t num_features, int32_t* __restrict__ out) {
   const int64_t S = (int64_t)gridDim.x * 256;
   for (int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x; t0 < n_tok; t0 += 4 * S) {
-    O b[4], e[4];
+    int64_t b[4], e[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int64_t t = t0 + q * S < n_tok ? t0 + q * S : n_tok - 1;
@@ -146,103 +149,20 @@ void hash_tokens(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off, int64_
     k_hash<false><<<g, 256, 0, c.stream>>>(d_utf8, d_tok_off, n_tok, num_features, d_idx);
   KERNEL_CHECK();
 }
-template <typename O>
-static void hash_tokens_t(Ctx& c, const uint8_t* d_utf8, const O* d_tok_off, int64_t n_tok, int32_t num_features,
-                          int variant, int32_t* d_idx) {
-  const int g = grid_for(ceil_div(n_tok, (int64_t)4), 256, 256 * 32);
-  if (variant == STC_HASH_SPARK24)
-    k_hash<true><<<g, 256, 0, c.stream>>>(d_utf8, d_tok_off, n_tok, num_features, d_idx);
-  else
-    k_hash<false><<<g, 256, 0, c.stream>>>(d_utf8, d_tok_off, n_tok, num_features, d_idx);
-  KERNEL_CHECK();
-}
 
 // ---------------------------------------------------------------------------------------
 // K2: per-document sort + run-length count → CSR.  One wave per document.
 //  pass A (k_doc_hash_sort, then k_doc_sort for 257–1024 tokens): documents of ≤ kSortCap tokens are
-//    bitonic-sorted in registers (≤ 256 tokens hashed straight into them) (P = m/64 keys per lane, m = the next power of two ≥ max(n, 64); partners
-//    j ≥ P across lanes by __shfl_xor, j < P inside the lane), written back sorted, and their distinct
+//    bitonic-sorted in registers (≤ 256 tokens hashed straight into them; wave_sort.h: P = m/64 keys per
+//    lane, m = the next power of two ≥ max(n, 64)), written back sorted, and their distinct
 //    ids counted into nnz[d].  Longer documents are hashed to memory and appended to a list for the
-//    segmented radix sort (hipcub), then counted by k_doc_runs<COUNT>.
+//    segmented radix sort (sort_long_docs), then counted by k_doc_runs<COUNT>.
 //  scan nnz → indptr; pass B (k_doc_runs<EMIT>): each document's sorted keys in 64-key chunks; run
 //    heads by ballot, output slots by mbcnt, run lengths from the next head in the chunk, or, for a
 //    chunk's last run, when the next chunk's first head (or the document end) arrives.
 // No atomics on the output; the large-document list is an atomic append whose order only permutes
 // hipcub's segments, so the CSR is bit-identical run to run.
 // ---------------------------------------------------------------------------------------
-constexpr int kSortCap = 1024;  // ≤ 16 keys per lane
-#ifndef TF_DPP
-#define TF_DPP 1  // the sort's cross-lane exchanges by DPP / swizzle (0: ds_bpermute throughout)
-#endif
-
-// x from lane ^ lx without the LDS crossbar where a DPP pattern exists (round 4: every shuffle of the
-// network was a ds_bpermute, ~60 % of the sort): xor 1 / 2 quad_perm, xor 4 = half-row mirror (xor 7)
-// after quad_perm xor 3, xor 8 = row rotate by 8; xor 16 ds_swizzle (no address VGPR); xor 32 bpermute.
-__device__ __forceinline__ int32_t shfl_xor_dpp(int32_t v, int lx) {
-  switch (lx) {
-    case 1: return __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    case 2: return __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    case 4: return __builtin_amdgcn_mov_dpp(__builtin_amdgcn_mov_dpp(v, 0x1B, 0xF, 0xF, false),  // [3,2,1,0]
-                                            0x141, 0xF, 0xF, false);     // row_half_mirror
-    case 8: return __builtin_amdgcn_mov_dpp(v, 0x128, 0xF, 0xF, false);  // row_ror:8
-    case 16: return __builtin_amdgcn_ds_swizzle(v, 0x401F);              // and 0x1F, xor 0x10
-    default: return __shfl_xor(v, lx, 64);
-  }
-}
-
-// Σ over the wave of a per-lane count in [0, P] from bit-sliced ballots (scalar popcounts, no shuffles)
-template <int P>
-__device__ __forceinline__ int wave_sum_small(int v) {
-  int tot = 0;
-#pragma unroll
-  for (int b = 0; (1 << b) <= P; ++b) tot += __popcll(__ballot((v >> b) & 1)) << b;
-  return tot;
-}
-// the exclusive prefix of such a count over the lanes below this one
-template <int P>
-__device__ __forceinline__ int wave_excl_small(int v) {
-  int pre = 0;
-#pragma unroll
-  for (int b = 0; (1 << b) <= P; ++b) {
-    const uint64_t m = __ballot((v >> b) & 1);
-    pre += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)) << b;
-  }
-  return pre;
-}
-
-template <int P>
-__device__ __forceinline__ void bitonic_regs(int32_t (&x)[P], int lane) {
-  constexpr int m = 64 * P;  // fully unrolled: every partner distance is a constant
-#pragma unroll
-  for (int k = 2; k <= m; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (j >= P) {  // partner in lane ^ (j / P), same register
-        const int lx = j / P;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          const int e = lane * P + p;
-          const int32_t o = TF_DPP ? shfl_xor_dpp(x[p], lx) : __shfl_xor(x[p], lx, 64);
-          const bool lower = (e & j) == 0, asc = (e & k) == 0;
-          x[p] = (lower == asc) ? min(x[p], o) : max(x[p], o);
-        }
-      } else {
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-          const int q = p ^ j;
-          if (q > p) {
-            const int e = lane * P + p;
-            const bool asc = (e & k) == 0;
-            const int32_t a = x[p], b = x[q];
-            x[p] = asc ? min(a, b) : max(a, b);
-            x[q] = asc ? max(a, b) : min(a, b);
-          }
-        }
-      }
-    }
-  }
-}
-
 template <int P>
 __device__ __forceinline__ int64_t sort_doc(const int32_t* __restrict__ keys, int32_t* __restrict__ sorted,
                                             int64_t s, int n, int lane) {
@@ -253,22 +173,14 @@ __device__ __forceinline__ int64_t sort_doc(const int32_t* __restrict__ keys, in
     x[p] = e < n ? keys[s + e] : INT32_MAX;  // pads sort last (bucket ids < numFeatures ≤ 2^31 − 1)
   }
   bitonic_regs<P>(x, lane);
-  const int32_t prev_last = __shfl_up(x[P - 1], 1, 64);
-  int heads = 0;
 #pragma unroll
   for (int p = 0; p < P; ++p) {
     const int e = lane * P + p;
-    if (e < n) {
-      sorted[s + e] = x[p];
-      const int32_t prev = p == 0 ? prev_last : x[p - 1];
-      heads += (e == 0 || x[p] != prev) ? 1 : 0;
-    }
+    if (e < n) sorted[s + e] = x[p];
   }
-  for (int o = 32; o > 0; o >>= 1) heads += __shfl_xor(heads, o, 64);
-  return heads;
+  return count_runs<P>(x, n, lane);
 }
 
-constexpr int kDocWaves = 4;  // documents in flight per workgroup (one per wave)
 constexpr int kFusedCap = 256;  // documents up to this many tokens are hashed and sorted in one pass
 
 // K1 fused into K2's pass A: the document's bucket ids never round-trip through HBM.  Token p·64 + lane
@@ -300,36 +212,7 @@ __device__ __forceinline__ int hash_sort_regs(const uint8_t* __restrict__ utf8, 
     if (p + 1 < P) cur = nxt;
   }
   bitonic_regs<P>(x, lane);
-  const int32_t prev_last = __shfl_up(x[P - 1], 1, 64);
-  int heads = 0;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const int q = lane * P + p;
-    const int32_t prev = p == 0 ? prev_last : x[p - 1];
-    heads += (q < n && (q == 0 || x[p] != prev)) ? 1 : 0;
-  }
-  return wave_sum_small<P>(heads);  // distinct ids (wave total)
-}
-
-// the same from bucket ids already hashed into `keys` (token order): load, sort, count distinct
-template <int P>
-__device__ __forceinline__ int keys_sort_regs(const int32_t* __restrict__ keys, int64_t s, int n, int32_t (&x)[P],
-                                              int lane) {
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const int q = p * 64 + lane;
-    x[p] = q < n ? keys[s + q] : INT32_MAX;  // pads sort last
-  }
-  bitonic_regs<P>(x, lane);
-  const int32_t prev_last = __shfl_up(x[P - 1], 1, 64);
-  int heads = 0;
-#pragma unroll
-  for (int p = 0; p < P; ++p) {
-    const int q = lane * P + p;
-    const int32_t prev = p == 0 ? prev_last : x[p - 1];
-    heads += (q < n && (q == 0 || x[p] != prev)) ? 1 : 0;
-  }
-  return wave_sum_small<P>(heads);
+  return count_runs<P>(x, n, lane);  // distinct ids (wave total)
 }
 
 template <bool SPARK24, int P, typename O>
@@ -377,9 +260,9 @@ __global__ __launch_bounds__(64 * kDocWaves, 8) void k_doc_hash_sort(const uint8
     }
     const int n = (int)n64;
     int64_t h = 0;
-    if (n <= 64) h = hash_sort_doc<SPARK24, 1, O>(utf8, tok_off, s, n, nf, sorted, lane);
-    else if (n <= 128) h = hash_sort_doc<SPARK24, 2, O>(utf8, tok_off, s, n, nf, sorted, lane);
-    else h = hash_sort_doc<SPARK24, 4, O>(utf8, tok_off, s, n, nf, sorted, lane);
+    with_keys_per_lane<1, kFusedCap / 64>(n, [&](auto pc) {
+      h = hash_sort_doc<SPARK24, decltype(pc)::value, O>(utf8, tok_off, s, n, nf, sorted, lane);
+    });
     if (lane == 0) nnz[d] = h;
   }
 }
@@ -391,10 +274,11 @@ __global__ __launch_bounds__(64 * kDocWaves, 8) void k_doc_hash_sort(const uint8
 // c, c + 8, … in order — so every tile a look-back waits on is held by a running workgroup, or is the
 // next one its counter hands out to a workgroup whose own look-back waits only on lower tiles (the
 // lowest unpublished tile always makes progress): no dependence on dispatch order or residency.  A look-back that waits past its poll bound sets the fault word; the host then rebuilds
-// the CSR with the sorted-key passes (mode 0).  Measured without gain: batching tickets (2–8 consecutive
+// the CSR with the sorted-key passes (what STC_TF_MODE=0 runs from the start).  Measured without gain: batching tickets (2–8 consecutive
 // tiles per atomic: 1.2× to 300× slower, a batch's later tiles publish their counts an iteration late)
 // and a static tile order over a resident grid (tile = step·grid + blockIdx: 2.89 vs 2.11 ms, a slow
-// workgroup stalls every later tile; and with the flat-hash mode the grid was not all resident).  status[t] = flag << 62 | value
+// workgroup stalls every later tile) and a flat hash of all tokens before a load + sort + emit pass
+// (0.77 + 1.55 ms against 2.11 ms; deleted).  status[t] = flag << 62 | value
 // (flag 1: the tile's own entry count, 2: the inclusive count of tiles 0..t), written by one lane with
 // agent-scope atomic stores and read with agent-scope atomic loads (vector memory, L2-coherent).
 constexpr uint64_t kLbAgg = 1ull << 62, kLbInc = 2ull << 62, kLbVal = kLbAgg - 1;
@@ -447,7 +331,7 @@ __device__ __forceinline__ int64_t tile_lookback(uint64_t* status, int64_t tile,
 template <int P, typename V>
 __device__ __forceinline__ void emit_runs(const int32_t (&x)[4], int n, int lane, int64_t out0, int binary,
                                           int32_t* __restrict__ idx, V* __restrict__ vals) {
-  const int32_t prev_last = __shfl_up(x[P - 1], 1, 64);
+  const int32_t prev_last = __shfl_up(x[P - 1], 1, 64);  // the heads as count_runs finds them, kept as flags
   bool hd[P];
   int hc = 0;
 #pragma unroll
@@ -487,23 +371,12 @@ __device__ __forceinline__ void emit_runs(const int32_t (&x)[4], int n, int lane
 // Pipelined one tile deep: a workgroup publishes tile t's count as soon as its documents are sorted, hashes
 // and sorts its next tile, and only then resolves t's offset and emits t — by then t's predecessors have
 // published, so the look-back seldom waits (the unpipelined form idled ~40 % of the time there).
-#ifndef TF_EMIT_OCC
-#define TF_EMIT_OCC 7  // waves per SIMD: 72 VGPRs; 8 spills two
-#endif
-#ifndef TF_EMIT_WAVES
-#define TF_EMIT_WAVES 8  // documents per tile (one per wave): one ticket and one look-back per tile (4: +30 %)
-#endif
-constexpr int kEmitWaves = TF_EMIT_WAVES;
+constexpr int kEmitOcc = 7;    // waves per SIMD: 72 VGPRs; 8 spills two
+constexpr int kEmitWaves = 8;  // documents per tile (one per wave): one ticket and one look-back per tile (4: +30 %)
+static_assert(kFusedCap == 64 * 4, "the single pass carries a document in int32_t x[4]");
 
-template <int P>
-__device__ __forceinline__ void take(int32_t (&x)[4], const int32_t (&xp)[P]) {
-#pragma unroll
-  for (int p = 0; p < P; ++p) x[p] = xp[p];
-}
-
-template <bool SPARK24, bool KEYS, typename V, typename O>
-__global__ __launch_bounds__(64 * kEmitWaves, TF_EMIT_OCC) void k_doc_hash_emit(
-    const int32_t* __restrict__ keys /* KEYS: the hashed ids, token order */,
+template <bool SPARK24, typename V, typename O>
+__global__ __launch_bounds__(64 * kEmitWaves, kEmitOcc) void k_doc_hash_emit(
     const uint8_t* __restrict__ utf8, const O* __restrict__ tok_off, const int64_t* __restrict__ doc_off,
     int64_t n_docs, int32_t nf, int binary, int64_t* __restrict__ indptr, int32_t* __restrict__ idx,
     V* __restrict__ vals, uint64_t* __restrict__ status, unsigned long long* __restrict__ ticket, int max_polls) {
@@ -531,19 +404,13 @@ __global__ __launch_bounds__(64 * kEmitWaves, TF_EMIT_OCC) void k_doc_hash_emit(
       if (d < n_docs) {
         const int64_t s = doc_off[d];
         n = (int)(doc_off[d + 1] - s);
-        if (n <= 64) {
-          int32_t xp[1];
-          h = KEYS ? keys_sort_regs<1>(keys, s, n, xp, lane) : hash_sort_regs<SPARK24, 1, O>(utf8, tok_off, s, n, nf, xp, lane);
-          take<1>(x, xp);
-        } else if (n <= 128) {
-          int32_t xp[2];
-          h = KEYS ? keys_sort_regs<2>(keys, s, n, xp, lane) : hash_sort_regs<SPARK24, 2, O>(utf8, tok_off, s, n, nf, xp, lane);
-          take<2>(x, xp);
-        } else {
-          int32_t xp[4];
-          h = KEYS ? keys_sort_regs<4>(keys, s, n, xp, lane) : hash_sort_regs<SPARK24, 4, O>(utf8, tok_off, s, n, nf, xp, lane);
-          take<4>(x, xp);
-        }
+        with_keys_per_lane<1, 4>(n, [&](auto pc) {
+          constexpr int P = decltype(pc)::value;
+          int32_t xp[P];
+          h = hash_sort_regs<SPARK24, P, O>(utf8, tok_off, s, n, nf, xp, lane);
+#pragma unroll
+          for (int p = 0; p < P; ++p) x[p] = xp[p];
+        });
       }
       if (lane == 0) wn[wv] = h;
     }
@@ -566,6 +433,7 @@ __global__ __launch_bounds__(64 * kEmitWaves, TF_EMIT_OCC) void k_doc_hash_emit(
       const int64_t d = tp * kEmitWaves + wv;
       if (d < n_docs) {
         const int64_t out0 = base_s + preq;
+        // (a plain chain: through with_keys_per_lane the kernel's register allocation moved)
         if (nq <= 64) emit_runs<1, V>(xq, nq, lane, out0, binary, idx, vals);
         else if (nq <= 128) emit_runs<2, V>(xq, nq, lane, out0, binary, idx, vals);
         else emit_runs<4, V>(xq, nq, lane, out0, binary, idx, vals);
@@ -593,12 +461,15 @@ __global__ __launch_bounds__(64 * kDocWaves) void k_doc_sort(const int32_t* __re
     const int64_t s = doc_off[d], n64 = doc_off[d + 1] - s;
     if (n64 <= kFusedCap || n64 > kSortCap) continue;
     const int n = (int)n64;
-    const int64_t h = n <= 512 ? sort_doc<8>(keys, sorted, s, n, lane) : sort_doc<16>(keys, sorted, s, n, lane);
+    int64_t h = 0;
+    with_keys_per_lane<2 * kFusedCap / 64, kSortCap / 64>(n, [&](auto pc) {
+      h = sort_doc<decltype(pc)::value>(keys, sorted, s, n, lane);
+    });
     if (lane == 0) nnz[d] = h;
   }
 }
 
-// segment bounds of the listed long documents (for hipcub's segmented sort) and their flags
+// segment bounds of the listed long documents (for hipcub's segmented sort) and, where asked for, their flags
 __global__ __launch_bounds__(256) void k_large_segments(const int32_t* __restrict__ large, int32_t n_large,
                                                         const int64_t* __restrict__ doc_off,
                                                         int64_t* __restrict__ beg, int64_t* __restrict__ end,
@@ -608,8 +479,26 @@ __global__ __launch_bounds__(256) void k_large_segments(const int32_t* __restric
     const int32_t d = large[i];
     beg[i] = doc_off[d];
     end[i] = doc_off[d + 1];
-    is_large[d] = 1;
+    if (is_large) is_large[d] = 1;
   }
+}
+
+void sort_long_docs(Ctx& c, const int32_t* d_keys, int32_t* d_sorted, int64_t n_tok, const int32_t* d_large,
+                    int32_t n_large, const int64_t* d_doc_off, int64_t max_key, DevBuf& seg, DevBuf& tmp,
+                    uint8_t* d_is_large) {
+  hipStream_t st = c.stream;
+  seg.reserve(sizeof(int64_t) * 2 * n_large);
+  int64_t* beg = seg.as<int64_t>();
+  int64_t* end = beg + n_large;
+  k_large_segments<<<(unsigned)ceil_div(n_large, 256), 256, 0, st>>>(d_large, n_large, d_doc_off, beg, end,
+                                                                     d_is_large);
+  KERNEL_CHECK();
+  int nbits = 1;
+  while ((int64_t(1) << nbits) <= max_key) ++nbits;
+  with_temp(tmp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceSegmentedRadixSort::SortKeys(t, tb, d_keys, d_sorted, (int)n_tok, n_large, beg, end, 0,
+                                                      nbits, st);
+  });
 }
 
 // the runs of one document's sorted keys, 64 at a time: COUNT → nnz[d]; EMIT → ids + run lengths at
@@ -712,11 +601,9 @@ __global__ __launch_bounds__(64 * kDocWaves) void k_row_order(const int64_t* __r
       continue;
     }
     const int n = (int)n64;
-    if (n <= 64) order_row<1>(idx, df, order, s, n, lane);
-    else if (n <= 128) order_row<2>(idx, df, order, s, n, lane);
-    else if (n <= 256) order_row<4>(idx, df, order, s, n, lane);
-    else if (n <= 512) order_row<8>(idx, df, order, s, n, lane);
-    else order_row<16>(idx, df, order, s, n, lane);
+    with_keys_per_lane<1, kSortCap / 64>(n, [&](auto pc) {
+      order_row<decltype(pc)::value>(idx, df, order, s, n, lane);
+    });
   }
 }
 
@@ -740,7 +627,20 @@ void narrow_offsets(Ctx& c, const int64_t* d_src, int64_t n, uint32_t* d_dst) {
   KERNEL_CHECK();
 }
 
-// the look-back single pass (modes 1 / 2); false: a look-back timed out, the caller runs the passes
+// resident workgroups per CU of one k_doc_hash_emit instantiation: the occupancy query once per kernel and process
+static int emit_blocks_per_cu(const void* kern) {
+  static std::mutex mu;
+  static std::map<const void*, int> occ;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = occ.find(kern);
+  if (it != occ.end()) return it->second;
+  int per_cu = 0;
+  HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kEmitWaves, 0));
+  occ[kern] = per_cu;
+  return per_cu;
+}
+
+// the look-back single pass; false: a look-back timed out, the caller runs the passes
 static bool single_pass(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off64, const uint32_t* d_tok_off32,
                         int64_t n_tok, const int64_t* d_doc_off, int64_t n_docs, int32_t num_features, int binary,
                         int variant, int value_dtype, DCsr& out) {
@@ -754,55 +654,21 @@ static bool single_pass(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off6
   // nnz ≤ n_tok: the output is sized before the counts exist
   c.recycle.take(out.indices, sizeof(int32_t) * n_tok);
   c.recycle.take(out.values, (value_dtype == STC_F32 ? 4 : 8) * n_tok);
-  // mode 1 (default): hashed inside the per-document pass; mode 2: the tokens hashed flat first (k_hash,
-  // four independent chains per lane), the per-document pass then loads, sorts and emits
-  const bool flat = c.tf_mode == 2;
-  int32_t* keys = nullptr;
-  if (flat) {
-    DevBuf& kb = c.scratch[0];
-    kb.reserve(sizeof(int32_t) * n_tok);
-    keys = kb.as<int32_t>();
-    if (d_tok_off32) hash_tokens_t(c, d_utf8, d_tok_off32, n_tok, num_features, variant, keys);
-    else hash_tokens_t(c, d_utf8, d_tok_off64, n_tok, num_features, variant, keys);
-  }
-  int max_polls = c.tf_force_fault ? 0 : kLbMaxPolls;
+  const int max_polls = c.tf_force_fault ? 0 : kLbMaxPolls;
   auto go = [&](auto spark, auto* vals) {
     constexpr bool S24 = decltype(spark)::value;
     using V = std::remove_pointer_t<decltype(vals)>;
-    auto launch = [&](const void* kern, auto tok_off) {
-      // a grid of what is resident (more workgroups would only take tickets past the end); the occupancy
-      // query once per kernel and process
-      static std::mutex mu;
-      static std::map<const void*, int> occ;
-      int per_cu = 0;
-      {
-        std::lock_guard<std::mutex> lk(mu);
-        auto it = occ.find(kern);
-        if (it == occ.end()) {
-          HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * kEmitWaves, 0));
-          occ[kern] = per_cu;
-        } else {
-          per_cu = it->second;
-        }
-      }
-      const int64_t resident = (int64_t)std::max(per_cu, 1) * c.cus;
+    auto launch = [&](auto* kern, auto* tok_off) {  // kern: the instantiation for tok_off's type (the compiler checks)
+      // a grid of what is resident (more workgroups would only take tickets past the end)
+      const int64_t resident = (int64_t)std::max(emit_blocks_per_cu((const void*)kern), 1) * c.cus;
       const unsigned g = (unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, resident));
       unsigned long long* ticket = reinterpret_cast<unsigned long long*>(status + tiles + kTicketPitch);
-      const uint8_t* u8 = d_utf8;
-      const int64_t* doff = d_doc_off;
-      int64_t nd = n_docs;
-      int32_t nf = num_features;
-      int bin = binary;
-      int64_t* ip = out.indptr.as<int64_t>();
-      int32_t* ix = out.indices.as<int32_t>();
-      V* vv = vals;
-      uint64_t* stp = status;
-      void* args[] = {&keys, &u8, &tok_off, &doff, &nd, &nf, &bin, &ip, &ix, &vv, &stp, &ticket, &max_polls};
-      HIP_CHECK(hipLaunchKernel(kern, dim3(g), dim3(64 * kEmitWaves), args, 0, st));
+      kern<<<g, 64 * kEmitWaves, 0, st>>>(d_utf8, tok_off, d_doc_off, n_docs, num_features, binary,
+                                          out.indptr.as<int64_t>(), out.indices.as<int32_t>(), vals, status, ticket,
+                                          max_polls);
     };
-    if (flat) launch((const void*)k_doc_hash_emit<S24, true, V, int64_t>, d_tok_off64);
-    else if (d_tok_off32) launch((const void*)k_doc_hash_emit<S24, false, V, uint32_t>, d_tok_off32);
-    else launch((const void*)k_doc_hash_emit<S24, false, V, int64_t>, d_tok_off64);
+    if (d_tok_off32) launch(k_doc_hash_emit<S24, V, uint32_t>, d_tok_off32);
+    else launch(k_doc_hash_emit<S24, V, int64_t>, d_tok_off64);
   };
   if (value_dtype == STC_F32) {
     if (variant == STC_HASH_SPARK24) go(std::true_type{}, out.values.as<float>());
@@ -841,7 +707,7 @@ void build_csr(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off64, const 
     out.nnz = 0;
     return;
   }
-  if (max_doc >= 0 && max_doc <= kFusedCap && c.tf_mode > 0 &&
+  if (max_doc >= 0 && max_doc <= kFusedCap && c.tf_single_pass &&
       single_pass(c, d_utf8, d_tok_off64, d_tok_off32, n_tok, d_doc_off, n_docs, num_features, binary, variant,
                   value_dtype, out))
     return;
@@ -889,22 +755,10 @@ void build_csr(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off64, const 
   DevBuf& tmp = c.scratch[8];
   if (n_large > 0) {  // long documents: hipcub segmented radix sort, then their run counts
     sorted_l.reserve(sizeof(int32_t) * n_tok);
-    seg.reserve(sizeof(int64_t) * 2 * n_large);
     flags.reserve(n_docs);
     HIP_CHECK(hipMemsetAsync(flags.p, 0, n_docs, st));
-    int64_t* beg = seg.as<int64_t>();
-    int64_t* end = beg + n_large;
-    k_large_segments<<<(unsigned)ceil_div(n_large, 256), 256, 0, st>>>(large, n_large, d_doc_off, beg, end,
-                                                                       flags.as<uint8_t>());
-    KERNEL_CHECK();
-    int nbits = 1;  // bucket ids < numFeatures
-    while ((int64_t(1) << nbits) < num_features) ++nbits;
-    size_t tb = 0;
-    HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, tb, keys.as<int32_t>(), sorted_l.as<int32_t>(),
-                                                         (int)n_tok, n_large, beg, end, 0, nbits, st));
-    tmp.reserve(tb);
-    HIP_CHECK(hipcub::DeviceSegmentedRadixSort::SortKeys(tmp.p, tb, keys.as<int32_t>(), sorted_l.as<int32_t>(),
-                                                         (int)n_tok, n_large, beg, end, 0, nbits, st));
+    sort_long_docs(c, keys.as<int32_t>(), sorted_l.as<int32_t>(), n_tok, large, n_large, d_doc_off,
+                   (int64_t)num_features - 1 /* bucket ids < numFeatures */, seg, tmp, flags.as<uint8_t>());
     k_doc_runs<false, float><<<(unsigned)std::min<int64_t>(ceil_div((int64_t)n_large, (int64_t)kDocWaves), 1 << 14), 64 * kDocWaves, 0, st>>>(
         sorted.as<int32_t>(), sorted_l.as<int32_t>(), flags.as<uint8_t>(), large, n_large, d_doc_off, n_docs,
         nullptr, binary, nullptr, nullptr, nnz.as<int64_t>() + 1);
@@ -912,12 +766,10 @@ void build_csr(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off64, const 
   }
   // indptr = [0, inclusive scan of nnz]
   HIP_CHECK(hipMemsetAsync(out.indptr.p, 0, sizeof(int64_t), st));
-  size_t sb = 0;
-  HIP_CHECK(hipcub::DeviceScan::InclusiveSum(nullptr, sb, nnz.as<int64_t>() + 1, out.indptr.as<int64_t>() + 1,
-                                             (int)n_docs, st));
-  stmp.reserve(sb);
-  HIP_CHECK(hipcub::DeviceScan::InclusiveSum(stmp.p, sb, nnz.as<int64_t>() + 1, out.indptr.as<int64_t>() + 1,
-                                             (int)n_docs, st));
+  with_temp(stmp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceScan::InclusiveSum(t, tb, nnz.as<int64_t>() + 1, out.indptr.as<int64_t>() + 1, (int)n_docs,
+                                            st);
+  });
   int64_t total = 0;
   HIP_CHECK(hipMemcpyAsync(&total, out.indptr.as<int64_t>() + n_docs, sizeof(int64_t), hipMemcpyDeviceToHost, st));
   HIP_CHECK(hipStreamSynchronize(st));

@@ -9,7 +9,7 @@
 // tiles in LDS instead (see there).
 #include <hipcub/hipcub.hpp>
 
-#include "stc_internal.h"
+#include "stc_handles.h"
 
 namespace stc {
 namespace idf {
@@ -25,118 +25,17 @@ static int grid_for(int64_t n) {
 // A Zipf corpus's hot ids sit in almost every row, and device-scope atomics run at a few G/s, so
 // the histogram is built without per-entry global atomics:
 //  * numFeatures ≤ 2^18: vocabulary tiles of 2^15 ids counted in LDS (128 KB of u32) per chunk group,
-//    partial histograms summed in group order by k_df_reduce.  k_df_tiled (default) streams a group's
-//    ids once per tile from L2; k_df_bin + k_df_binned (round 3, STC_DF_BINNED=1) first split each
-//    chunk by tile into a u16 bin array.
+//    partial histograms summed in group order by k_df_reduce.  k_df_tiled streams a group's ids once
+//    per tile from L2; k_df_rows16 does the same over 2^16-id tiles for rows that hold an id at most once.
+//    (Round 3 first split each chunk by tile into a u16 bin array: 0.77 + 0.41 ms against 0.33 ms, deleted.)
 //  * larger vocabularies: the (value > 0) ids are radix-sorted and each run's [lo, hi) recorded.
-// Both are exact integer counts, identical run to run.
+// All are exact integer counts, identical run to run; which one runs depends on the matrix alone.
 constexpr int kTileBits = 15;
 constexpr int kTile = 1 << kTileBits;
-constexpr int kTileThreads = 1024;
 
-// Binned variant (one read of the CSR): k_df_bin splits each chunk of kBinChunk entries by tile —
-// the (value > 0) ids' low 15 bits as u16, tile-major inside the chunk's own region of the bin array
-// (no global scan: a chunk's region is its kBinChunk slots) — and k_df_binned counts one tile over a
-// group of chunks in LDS.  Bytes per entry: 4 + s (id, value) read, 2 written, 2 read.
-constexpr int kBinChunk = 16384;
-constexpr int kBinThreads = 1024;
-constexpr int kBinPer = kBinChunk / kBinThreads;  // entries per thread
 constexpr int kMaxTiles = 8;  // numFeatures ≤ 2^18 (32 tiles for 2^20 measured 2.2× slower than the sort)
 
-template <typename V, int MT>
-__global__ __launch_bounds__(kBinThreads) void k_df_bin(const int32_t* __restrict__ idx, const V* __restrict__ val,
-                                                        int64_t nnz, int n_tiles, uint16_t* __restrict__ bins,
-                                                        int32_t* __restrict__ tab /* [chunk][2·kMaxTiles] */) {
-  __shared__ int32_t wtot[kBinThreads / 64][MT];
-  __shared__ int32_t tbase[MT + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t c = blockIdx.x, e0 = c * kBinChunk;
-  uint32_t ent[kBinPer];  // tile << 16 | low id, or ~0u
-  int cnt[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) cnt[t] = 0;
-#pragma unroll
-  for (int u = 0; u < kBinPer; ++u) {
-    const int64_t e = e0 + u * kBinThreads + tid;
-    uint32_t x = ~0u;
-    if (e < nnz && (val == nullptr || val[e] > V(0))) {  // val = nullptr: every value is known > 0
-      const uint32_t id = (uint32_t)idx[e];
-      x = ((id >> kTileBits) << 16) | (id & (kTile - 1));
-    }
-    ent[u] = x;
-#pragma unroll
-    for (int t = 0; t < MT; ++t) cnt[t] += (x >> 16) == (uint32_t)t ? 1 : 0;
-  }
-  // exclusive prefix of each tile's counts over the block's threads (thread order)
-  int pre[MT];
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    int v = cnt[t];
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(v, o, 64);
-      if (lane >= o) v += y;
-    }
-    pre[t] = v - cnt[t];
-    if (lane == 63) wtot[wave][t] = v;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int run = 0;
-    for (int t = 0; t < MT; ++t) {
-      tbase[t] = run;
-      int tot = 0;
-      for (int w = 0; w < kBinThreads / 64; ++w) tot += wtot[w][t];
-      tab[c * 2 * kMaxTiles + t] = run;                 // the tile's offset inside the chunk region
-      tab[c * 2 * kMaxTiles + kMaxTiles + t] = tot;     // and its count
-      run += tot;
-    }
-    tbase[MT] = run;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int t = 0; t < MT; ++t) {
-    int wb = 0;
-    for (int w = 0; w < wave; ++w) wb += wtot[w][t];
-    pre[t] += tbase[t] + wb;
-  }
-  uint16_t* out = bins + e0;
-#pragma unroll
-  for (int u = 0; u < kBinPer; ++u) {
-    const uint32_t x = ent[u];
-    if (x != ~0u) {
-      const int t = (int)(x >> 16);
-      int pos = 0;
-#pragma unroll
-      for (int q = 0; q < MT; ++q)
-        if (q == t) pos = pre[q]++;
-      out[pos] = (uint16_t)(x & 0xFFFF);
-    }
-  }
-}
-
-__global__ __launch_bounds__(kTileThreads) void k_df_binned(const uint16_t* __restrict__ bins,
-                                                            const int32_t* __restrict__ tab, int64_t chunks,
-                                                            int64_t per_group, int n_tiles, int64_t cols,
-                                                            uint32_t* __restrict__ part) {
-  extern __shared__ uint32_t cnt[];
-  const int t = blockIdx.x % n_tiles;
-  const int64_t g = blockIdx.x / n_tiles;
-  for (int i = threadIdx.x; i < kTile; i += kTileThreads) cnt[i] = 0;
-  __syncthreads();
-  const int64_t c0 = g * per_group, c1 = c0 + per_group < chunks ? c0 + per_group : chunks;
-  for (int64_t c = c0; c < c1; ++c) {
-    const int32_t off = tab[c * 2 * kMaxTiles + t], n = tab[c * 2 * kMaxTiles + kMaxTiles + t];
-    const uint16_t* b = bins + c * kBinChunk + off;
-    for (int i = threadIdx.x; i < n; i += kTileThreads) atomicAdd(&cnt[b[i]], 1u);
-  }
-  __syncthreads();
-  const int64_t j0 = (int64_t)t * kTile;
-  uint32_t* out = part + g * cols + j0;
-  for (int i = threadIdx.x; i < kTile && j0 + i < cols; i += kTileThreads) out[i] = cnt[i];
-}
-
-// Tiled variant (round 4, the default for numFeatures ≤ 2^18): no bin array.  Workgroup (g, t) streams
+// Tiled count (round 4, numFeatures ≤ 2^18).  Workgroup (g, t) streams
 // the whole index range of chunk group g and counts the ids of vocabulary tile t in LDS; the T
 // workgroups of one group are placed on one XCD (blockIdx % 8 picks the XCD) and start together, so
 // the group's indices come from HBM once and are re-read T times from that XCD's L2.  Bytes per
@@ -310,8 +209,7 @@ bool doc_freq(Ctx& c, const DCsr& m, int64_t* d_df, const IdfFinal* fin) {
     HIP_CHECK(hipMemsetAsync(d_df, 0, sizeof(int64_t) * m.cols, s));
     return false;
   }
-  if (m.unique_ids && m.cols <= (int64_t(kMaxTiles / 2) << kTile16Bits) && c.df_tiled && c.df_rows16 &&
-      m.rows > 0) {
+  if (m.unique_ids && m.cols <= (int64_t(kMaxTiles / 2) << kTile16Bits) && m.rows > 0) {
     const int T = (int)ceil_div(m.cols, (int64_t)1 << kTile16Bits);
     const int64_t want = std::max<int64_t>(1, (int64_t)c.cus / T);
     int64_t G = std::max<int64_t>(std::min<int64_t>(want, ceil_div(m.nnz, (int64_t)65536)), 1);
@@ -329,7 +227,7 @@ bool doc_freq(Ctx& c, const DCsr& m, int64_t* d_df, const IdfFinal* fin) {
     KERNEL_CHECK();
     return fin != nullptr;
   }
-  if (m.cols <= (int64_t(kMaxTiles) << kTileBits) && c.df_tiled) {
+  if (m.cols <= (int64_t(kMaxTiles) << kTileBits)) {
     const int T = (int)ceil_div(m.cols, (int64_t)kTile);
     // groups: a multiple of 8 (the XCD mapping) with T·groups ≈ one workgroup per CU, fewer for small
     // inputs (≥ 64 Ki entries per group)
@@ -360,41 +258,6 @@ bool doc_freq(Ctx& c, const DCsr& m, int64_t* d_df, const IdfFinal* fin) {
     KERNEL_CHECK();
     return fin != nullptr;
   }
-  if (m.cols <= (int64_t(kMaxTiles) << kTileBits)) {
-    const int T = (int)ceil_div(m.cols, (int64_t)kTile);
-    const int64_t chunks = ceil_div(m.nnz, (int64_t)kBinChunk);
-    const int64_t G = std::max<int64_t>(1, std::min<int64_t>(chunks, 1024 / T));  // chunk groups
-    const int64_t per_group = ceil_div(chunks, G);
-    const int64_t groups = ceil_div(chunks, per_group);
-    DevBuf& bins = c.scratch[1];
-    DevBuf& tab = c.scratch[2];
-    DevBuf& part = c.scratch[0];
-    bins.reserve(sizeof(uint16_t) * chunks * kBinChunk);
-    tab.reserve(sizeof(int32_t) * chunks * 2 * kMaxTiles);
-    part.reserve(sizeof(uint32_t) * groups * m.cols);
-    // a CSR whose values are all known > 0 (HashingTF output) is counted from its indices alone
-    auto bin = [&](auto mt) {
-      constexpr int MT = decltype(mt)::value;
-      if (m.dtype == STC_F32)
-        k_df_bin<float, MT><<<(unsigned)chunks, kBinThreads, 0, s>>>(
-            m.indices.as<int32_t>(), m.positive ? nullptr : m.values.as<float>(), m.nnz, T, bins.as<uint16_t>(),
-            tab.as<int32_t>());
-      else
-        k_df_bin<double, MT><<<(unsigned)chunks, kBinThreads, 0, s>>>(
-            m.indices.as<int32_t>(), m.positive ? nullptr : m.values.as<double>(), m.nnz, T, bins.as<uint16_t>(),
-            tab.as<int32_t>());
-    };
-    bin(std::integral_constant<int, kMaxTiles>{});
-    KERNEL_CHECK();
-    const size_t lds = sizeof(uint32_t) * kTile;
-    HIP_CHECK(hipFuncSetAttribute((const void*)k_df_binned, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    k_df_binned<<<(unsigned)(T * groups), kTileThreads, lds, s>>>(bins.as<uint16_t>(), tab.as<int32_t>(), chunks,
-                                                                  per_group, T, m.cols, part.as<uint32_t>());
-    KERNEL_CHECK();
-    k_df_reduce<<<grid_for(m.cols), 256, 0, s>>>(part.as<uint32_t>(), groups, m.cols, d_df, fin_m, fin_min, fin_idf);
-    KERNEL_CHECK();
-    return fin != nullptr;
-  }
   STC_REQUIRE(m.nnz < (int64_t(1) << 31), "idf: at most 2^31-1 entries per call");
   HIP_CHECK(hipMemsetAsync(d_df, 0, sizeof(int64_t) * m.cols, s));  // k_runs adds into it
   const uint32_t sentinel = (uint32_t)m.cols;
@@ -412,12 +275,9 @@ bool doc_freq(Ctx& c, const DCsr& m, int64_t* d_df, const IdfFinal* fin) {
     k_keys<double><<<grid_for(m.nnz), 256, 0, s>>>(m.indices.as<int32_t>(), m.values.as<double>(), m.nnz, sentinel,
                                                    keys.as<uint32_t>());
   KERNEL_CHECK();
-  size_t tb = 0;
-  HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, keys.as<uint32_t>(), sorted.as<uint32_t>(), (int)m.nnz, 0,
-                                              nbits, s));
-  tmp.reserve(tb);
-  HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(tmp.p, tb, keys.as<uint32_t>(), sorted.as<uint32_t>(), (int)m.nnz, 0,
-                                              nbits, s));
+  with_temp(tmp, [&](void* t, size_t& tb) {
+    return hipcub::DeviceRadixSort::SortKeys(t, tb, keys.as<uint32_t>(), sorted.as<uint32_t>(), (int)m.nnz, 0, nbits, s);
+  });
   k_runs<<<grid_for(m.nnz), 256, 0, s>>>(sorted.as<uint32_t>(), m.nnz, sentinel, d_df);
   KERNEL_CHECK();
   HIP_CHECK(hipStreamSynchronize(s));  // tmp dies at scope exit
@@ -488,17 +348,11 @@ __global__ __launch_bounds__(256) void k_transform(const int32_t* __restrict__ i
 // slots (id mod 2^14), the idf of the slot's highest-df id and that id's tag (id >> 14, u8), so a
 // workgroup holds 144 KB of the table in LDS and gathers from L2 only on a tag miss.  Config 2: ~75 %
 // of entries hit.  Tags need ids < 2^21 (numFeatures ≤ 2^21; larger vocabularies use k_transform).
-#ifndef IDF_CACHE_BITS
-#define IDF_CACHE_BITS 14  // 2^14 slots, 144 KB: one workgroup per CU
-#endif
-constexpr int kCacheBits = IDF_CACHE_BITS;
-constexpr int kCacheWgPerCu = IDF_CACHE_BITS <= 13 ? 2 : 1;  // workgroups whose tables fit a CU's LDS
+constexpr int kCacheBits = 14;  // 2^14 slots, 144 KB: one workgroup per CU
+constexpr int kCacheWgPerCu = kCacheBits <= 13 ? 2 : 1;  // workgroups whose tables fit a CU's LDS
 constexpr int kCacheSlots = 1 << kCacheBits;
 constexpr int kCacheThreads = 1024;
-#ifndef IDF_CACHE_UNROLL
-#define IDF_CACHE_UNROLL 4
-#endif
-constexpr int kCacheUnroll = IDF_CACHE_UNROLL;  // quads per thread and step (2: 0.81 ms)
+constexpr int kCacheUnroll = 4;  // quads per thread and step (2: 0.81 ms)
 constexpr uint8_t kCacheEmpty = 0xFF;
 
 __global__ __launch_bounds__(256) void k_idf_cache(const int64_t* __restrict__ df, const double* __restrict__ idf,

@@ -158,12 +158,10 @@ struct Ctx {
   int n_ranks = 1;
   int rank = 0;
   int cus = 256;          // compute units (the df count sizes its grid to one workgroup per CU)
-  bool df_tiled = true;   // idf.hip doc_freq: the tiled count (false: the binned one, STC_DF_BINNED=1)
-  bool df_rows16 = true;  // … its row-grouped u16 form for unique-id rows (STC_DF_U32=1: off)
-  // hashing_tf.hip build_csr when every document fits the register sort (STC_TF_MODE): 0 the round-3
-  // passes (hash + sort → sorted keys, scan, runs), 1 (default) hash + sort + emit in one look-back pass,
-  // 2 a flat hash then the look-back sort + emit pass
-  int tf_mode = 1;
+  // hashing_tf.hip build_csr when every document fits the fused register sort: hash + sort + emit in one
+  // look-back pass (STC_TF_MODE=0: false, the passes hash + sort → sorted keys, scan, runs — which longer
+  // documents and a timed-out look-back take anyway)
+  bool tf_single_pass = true;
   bool tf_force_fault = false;  // test knob (STC_TF_FAULT=1): every look-back gives up at once
   int64_t tf_fallbacks = 0;     // single passes that fell back to the sorted-key passes
   bool idf_cache = true;  // idf.hip: the device IDF model's hot-idf LDS table (STC_IDF_NO_CACHE=1: off)
@@ -246,6 +244,12 @@ namespace hashing {
 void hash_tokens(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off, int64_t n_tok,
                  int32_t num_features, int variant, int32_t* d_idx);
 void row_order_by_df(Ctx& c, const DCsr& m, const int64_t* d_df, int32_t* d_order);
+// the documents listed in d_large (n_large of them, each past the register sort's 1024 keys): d_sorted = d_keys
+// sorted inside each listed document's [doc_off[d], doc_off[d+1]) (hipcub's segmented radix sort over the bits of
+// max_key, the largest key); d_is_large[d] = 1 for each when given.  seg and tmp are the caller's scratch.
+void sort_long_docs(Ctx& c, const int32_t* d_keys, int32_t* d_sorted, int64_t n_tok, const int32_t* d_large,
+                    int32_t n_large, const int64_t* d_doc_off, int64_t max_key, DevBuf& seg, DevBuf& tmp,
+                    uint8_t* d_is_large = nullptr);
 // token offsets as int64 (d_tok_off64) or, when d_tok_off32 is given, u32 (a resident upload's narrowed copy)
 void build_csr(Ctx& c, const uint8_t* d_utf8, const int64_t* d_tok_off64, const uint32_t* d_tok_off32, int64_t n_tok,
                const int64_t* d_doc_off, int64_t n_docs, int32_t num_features, int binary,

@@ -185,9 +185,9 @@ def test_idf_doc_freq_zipf_hot_ids(ctx, V):
 
 @pytest.mark.parametrize("V", [1000, (1 << 15) + 3, 1 << 18])
 @pytest.mark.parametrize("D", [3, 7001])
-def test_idf_doc_freq_tiled_and_binned(ctx, monkeypatch, V, D):
-    """doc_freq's two LDS-tile counts (idf.hip: k_df_tiled, the default, one XCD's workgroups sharing a
-    chunk group's index stream; k_df_bin + k_df_binned under STC_DF_BINNED=1) and HashingTF's single
+def test_idf_doc_freq_tiled_and_tf_passes(ctx, monkeypatch, V, D):
+    """doc_freq's LDS-tile counts (idf.hip: k_df_rows16 on the HashingTF output, k_df_tiled on the uploaded
+    matrix, one XCD's workgroups sharing a group's index stream) on two contexts, HashingTF's single
     look-back pass vs its sorted-key passes (STC_TF_MODE=0, same CSR), and the transform with the
     model's hot-idf LDS table (default) and without it (STC_IDF_NO_CACHE=1) on a device-resident
     HashingTF matrix (values known positive: indices only) and on an uploaded matrix with explicit zeros
@@ -195,11 +195,10 @@ def test_idf_doc_freq_tiled_and_binned(ctx, monkeypatch, V, D):
     import stc
     from stc import synth
 
-    monkeypatch.setenv("STC_DF_BINNED", "1")
     monkeypatch.setenv("STC_TF_MODE", "0")
     monkeypatch.setenv("STC_IDF_NO_CACHE", "1")
     ctx_b = stc.Context(ctx.device)  # reads the knobs at stc_init
-    for k in ("STC_DF_BINNED", "STC_TF_MODE", "STC_IDF_NO_CACHE"):
+    for k in ("STC_TF_MODE", "STC_IDF_NO_CACHE"):
         monkeypatch.delenv(k)
     (blob, tok_off, doc_off), _ = synth.token_corpus(D, 150, n_words=40000, seed=11)
     csr = []
@@ -253,8 +252,7 @@ def test_hash_window_lengths_and_alignments(ctx, oracle, algo, variant):
 
 
 def test_hashing_tf_single_pass_orders_and_fallback(ctx, monkeypatch):
-    """HashingTF's look-back single pass (hashing_tf.hip single_pass; default), with the flat hash first
-    (STC_TF_MODE=2), and with every look-back
+    """HashingTF's look-back single pass (hashing_tf.hip single_pass; default), and with every look-back
     giving up at once (STC_TF_FAULT=1: the call falls back to the sorted-key passes and still succeeds):
     the same CSR as the sorted-key passes (STC_TF_MODE=0), bit for bit."""
     import stc
@@ -262,8 +260,7 @@ def test_hashing_tf_single_pass_orders_and_fallback(ctx, monkeypatch):
 
     (blob, tok_off, doc_off), _ = synth.token_corpus(3001, 120, n_words=30000, seed=21)
     got = {}
-    for tag, env in [("single", {}), ("flat", {"STC_TF_MODE": "2"}),
-                     ("fault", {"STC_TF_FAULT": "1"}), ("passes", {"STC_TF_MODE": "0"})]:
+    for tag, env in [("single", {}), ("fault", {"STC_TF_FAULT": "1"}), ("passes", {"STC_TF_MODE": "0"})]:
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         c = stc.Context(ctx.device)
