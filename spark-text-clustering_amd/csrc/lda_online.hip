@@ -658,6 +658,10 @@ void mixed_resolve(stc_lda& L, int64_t n, int64_t E, int64_t iteration, const do
   a.indptr = m.indptr.as<int64_t>();
   a.indices = m.indices.as<int32_t>();
   a.values = m.values.as<double>();
+  // the fp32 pass's row order (estep_and_stats): entry e0 + n of a document is then the same term in r64, in the
+  // fixup's sort values and in the fp32 pass's keys, which the fixup leaves in place.  None at k ≤ 128 (the fp32
+  // grid kernel wrote CSR positions); the workgroup kernel reads none in either pass.
+  a.order = L.order_for == L.corpus ? L.order.as<int32_t>() : nullptr;
   a.gamma0 = g0_64;
   a.iteration = iteration;
   a.key_mode = 0;

@@ -9,7 +9,8 @@ Checked against the two pure-precision handles on the same Î», documents and Î³â
   * the launch counters count exactly the documents above the threshold, through both re-solve lists (the
     fp64 fast kernel's documents and, past its row capacity, the workgroup kernel's).
 The north-star bars (topicsMatrix 1e-4, logPerplexity 1e-5, identical top-10 terms) for this mode are in
-tests/test_gpu_config1.py."""
+tests/test_gpu_config1.py.  The sufficient statistics of re-solved documents, and mixed training steps at every
+kernel width from k = 2 to 4096 (these tests stop at k = 100), are in tests/test_gpu_mixed_range.py."""
 import numpy as np
 import pytest
 

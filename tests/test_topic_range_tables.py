@@ -155,6 +155,70 @@ def test_alpha_step_widths():
     assert m and int(m.group(1)) == max(T.K)
 
 
+def test_mixed_k_list_follows_the_sources():
+    """tests/test_gpu_mixed_range.py's MIXED_K: a k on each side of every width at which a mixed step changes
+    instantiation — the fp64 re-solve's family (rows64 and its KL dispatch, then the many-topic kernel), the fp32
+    first pass's (grid, then the many-topic kernel and its row order), the many-topic kernel's limit — and, inside
+    each rows64 instantiation, a k whose fp32 pitch (the one the re-solve runs at) is not the fp64 pitch."""
+    import test_gpu_mixed_range as M
+
+    ks = M.MIXED_K
+    rows64 = _src("lda_rows64.hip")
+    m = re.search(r"int rows64_row_cap\(int k\) \{ return k <= (\d+) \? 32 \* kMaxSets : 0; \}", rows64)
+    rows64_limit = int(m.group(1))
+    body = rows64[rows64.index("void launch_estep_rows64("):]
+    kl = [(int(a), int(b)) for a, b in re.findall(r"if \(a\.k <= (\d+)\) launch_r<(\d+), kOne>", body)]
+    assert kl == [(32, 4), (56, 7)], kl
+    assert "else if (kTwo == 0 || a.kp > 64) launch_r<13, kTwo>" in body and "else launch_r<13, kOne>" in body
+    assert "if (a.kp > 8 * 13 || a.kp < a.k || (a.kp & 1)) throw" in body and rows64_limit == 8 * 13
+    kl.append((rows64_limit, 13))
+    grid = _src("lda_grid.hip")
+    body = grid[grid.index("int grid_row_cap(int k) {"):grid.index("int grid_onchip_rows(int k)")]
+    grid_limit = max(int(x) for x in re.findall(r"if \(k <= (\d+)\) return 32 \* G\w+::RMAX;", body))
+    assert "return 0;" in body and grid_limit == 128
+    wide = _src("lda_wide.hip")
+    assert "int wide_row_cap(int k) { return k <= kWThreads * 4 ? kWRows : 0; }" in wide
+    wide_limit = 4 * _const(wide, "kWThreads")
+    assert (rows64_limit, grid_limit, wide_limit) == (104, 128, 2048)
+    for limit in (rows64_limit, grid_limit, wide_limit):  # the last k of a family and the first of the next
+        assert limit in ks and limit + 1 in ks, limit
+    assert any(rows64_limit < k <= grid_limit for k in ks)  # fp32 grid, fp64 many-topic kernel
+    lo = 0
+    for hi, width in kl:  # every rows64 instantiation, with a k whose two pitches differ
+        inside = [k for k in ks if lo < k <= hi]
+        assert inside and any(-(-k // 4) * 4 != -(-k // 2) * 2 for k in inside), (width, inside)
+        assert all(-(-k // 4) * 4 <= 8 * width for k in inside), (width, inside)  # the fp32 pitch fits the slices
+        lo = hi
+    # KL = 13 runs with one ψ wave at kp ≤ 64 and two beyond: the differing pitch in both
+    wide13 = [k for k in ks if kl[1][0] < k <= rows64_limit and -(-k // 4) * 4 != -(-k // 2) * 2]
+    assert any(-(-k // 4) * 4 <= 64 for k in wide13) and any(-(-k // 4) * 4 > 64 for k in wide13), wide13
+    # the many-topic kernel's Q = 1 | 2 | 4 topics per lane, and the limit of the API
+    threads = _const(wide, "kWThreads")
+    for edge in (threads, 2 * threads):
+        assert edge in ks and edge + 1 in ks, edge
+    assert min(ks) == min(T.K) and max(ks) == max(T.K)
+    # the λ-update (it writes the Bp64 rows) and sstats instantiations at the fp32 pitch: those K reaches
+    assert {_lambda_q(kp) for kp in _kps(ks, PAD["f32"])} == {_lambda_q(kp) for kp in _kps(T.K, PAD["f32"])}
+    assert {1 << (-(-kp // 64) - 1).bit_length() for kp in _kps(ks, 4) if kp <= 256} == {1, 2, 4}  # sstats Q
+    assert {1, 2, 3} <= {-(-kp // 512) for kp in _kps(ks, 4)} and any(kp > 512 and kp % 512 for kp in _kps(ks, 4))
+    # the other cases' k: every k has a threshold percentile, the fixed lists sit in the families they name
+    assert set(ks) | set(M.SLICED_K) | {M.GROUP_K} == set(M.RESOLVE_PCT)
+    assert any(k <= rows64_limit for k in M.ALL_RESOLVED_K) and any(k > wide_limit for k in M.ALL_RESOLVED_K)
+    assert any(grid_limit < k <= wide_limit for k in M.ALL_RESOLVED_K)
+    assert [rows64_limit < k <= grid_limit for k in M.BOTH_LISTS_K] == [True, False, False]
+    assert all(k <= wide_limit for k in M.BOTH_LISTS_K)
+    rows = _const(wide, "kWRows")
+    g128 = re.search(r"using G128 = GShape<\d+, \d+, (\d+), \d+>;", grid)
+    assert "if (k <= 128) return 32 * G128::RMAX;" in grid
+    grid_rows = 32 * int(g128.group(1))  # grid_row_cap(120)
+    for edge in (rows, grid_rows):
+        assert edge in M.LIST_LENGTHS and edge + 1 in M.LIST_LENGTHS, edge
+    assert rows - 1 in M.LIST_LENGTHS and 0 in M.LIST_LENGTHS and max(M.LIST_LENGTHS) < M.LIST_V
+    assert f"L->cfg.max_inner_iter = {M.ITER_CAP};" in _src("lda_online.hip")
+    assert {_lambda_q(kp) for kp in _kps(M.SLICED_K, 4)} == {("k_lambda_eeb", 2), ("k_lambda_eeb", 4),
+                                                            ("k_lambda_eeb_wide", 4)}
+
+
 def test_shape_and_describe_cases():
     assert (T.V, T.D, T.BATCH, T.STEPS, T.FRAC) == (200, 40, 24, 3, 0.4)
     assert set(T.DESCRIBE_K) == {min(T.K), 100, max(T.K)}
