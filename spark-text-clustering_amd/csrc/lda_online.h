@@ -1,5 +1,6 @@
 // lda_online.h — what stc_group (group.hip) needs of its members' online-LDA handles beyond the public ABI.
-// struct stc_lda itself stays private to lda_online.hip.
+// struct stc_lda itself stays private to the handle's own translation units (lda_handle.h); these are defined in
+// lda_train.hip.
 #pragma once
 
 #include "stc_internal.h"

@@ -4,7 +4,7 @@ The product shards a minibatch by document.  E
 * runs the E-step on its members;
 * accumulates its partial `stat` (V×k), logphat and non-empty count;
 * joins a reduce-scatter of `stat` over vocabulary slices of Vs rows (Vs a multiple of the 64-row
-  λ-update block) grouped with the all-reduce of logphat / count (lda_online.hip train_tail);
+  λ-update block) grouped with the all-reduce of logphat / count (lda_train.hip train_tail);
 * updates λ on its slice, all-gathers the per-block colsum partials (reduced in block order, so every
   rank holds the same colsum), computes its slice of expElogβ and all-gathers it for the next E-step;
 * gathers λ only when a reader asks (gather_lambda); the bound sums each slice's topics part.

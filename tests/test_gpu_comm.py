@@ -78,7 +78,7 @@ def test_two_ranks_lda_next_idf_bound(tmp_path, oracle):
     st = oracle.OnlineLDAState(lam=lam0.T.copy(), alpha=alpha, eta=eta, corpus_size=total,
                                mini_batch_fraction=W.FRACTION, optimize_doc_concentration=True)
     empty_rank1 = 0
-    # next_impl (lda_online.hip): the membership is keyed by the DRAW counter, which advances on every call
+    # next_impl (lda_train.hip): the membership is keyed by the DRAW counter, which advances on every call
     # (Spark's generator advances on empty batches too); γ₀ by the iteration the batch would make
     for draw in range(1, W.STEPS + 1):
         it = st.iteration + 1

@@ -316,7 +316,7 @@ def test_group_transport_kinds(ctx, monkeypatch):
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_chunked_reduce_scatter_is_bitwise_the_single_one(ctx, monkeypatch, dtype):
-    """The sharded step with the stat reduce-scatter split into vocabulary sub-chunks (lda_online.hip
+    """The sharded step with the stat reduce-scatter split into vocabulary sub-chunks (lda_train.hip
     train_tail_split: one sstats launch per sub-chunk, each sub-chunk's reduce-scatter on the collective
     stream under the next sstats launch, the M-step of sub-chunk j under the reduce-scatter of j+1)
     against STC_RS_CHUNKS=1 (one reduce-scatter after the whole stat): λ, α, expElogβ'-dependent

@@ -1,6 +1,6 @@
 """GPU: the mixed mode (STC_MIXED) — the fp32 E-step for every document, then the documents
 whose fp32 fixed point took more than `mixed_resolve_iters` iterations re-solved in fp64 from the same γ₀
-(lda_online.hip mixed_resolve).
+(lda_dispatch.hip mixed_resolve).
 
 Checked against the two pure-precision handles on the same λ, documents and γ₀:
   * a re-solved document (fp32 iterations above the threshold) is the fp64 handle's: same iteration count,

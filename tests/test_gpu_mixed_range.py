@@ -1,7 +1,7 @@
 """Mixed-mode training steps vs the oracle at every kernel width from k = 2 to the limit k = 4096.
 
 dtype="mixed" runs the fp32 E-step for every document and re-solves in fp64 the documents whose fp32 fixed point
-took more than `mixed_resolve_iters` iterations (lda_online.hip mixed_resolve).  A mixed step
+took more than `mixed_resolve_iters` iterations (lda_dispatch.hip mixed_resolve).  A mixed step
 therefore runs two E-step families per k, and the fp64 one at the fp32 row pitch (kp: k rounded up to 4):
   fp32 first pass      grid k ≤ 128, the many-topic kernel to k = 2048 (from k = 129 a row's entries are taken
                        in the df-ascending row order), the workgroup kernel beyond

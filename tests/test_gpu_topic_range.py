@@ -7,7 +7,7 @@ fp32) into one instantiation per stage:
   sufficient statistics       Q = 1, 2, 4 (kp ≤ 64, 128, 256), then slabs of 256 (fp64) / 512 (fp32) columns,
                               up to 16 of them                                               lda_sstats.hip
   E-step                      fp64 rows64 k ≤ 104 / fp32 grid k ≤ 128, the many-topic kernel to k = 2048 (Q = 1, 2,
-                              4), the workgroup kernel k_estep for every document beyond     lda_online.hip
+                              4), the workgroup kernel k_estep for every document beyond     lda_dispatch.hip
   α Newton step, logphat      one pass per thread to k = 256, strided loops beyond
 K has a value on each side of every one of those widths in both paddings (tests/test_topic_range_tables.py reads
 the widths from the sources and checks that), the minimum, an odd k with a padding column, the headline k = 100

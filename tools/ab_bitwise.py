@@ -1,14 +1,17 @@
 """A/B parity of two builds of libstc: the same E-step + a few next() steps, outputs compared bit for bit.
 
     python tools/ab_bitwise.py LIB_A LIB_B [--docs N] [--len TOKENS] [--k K] [--vocab V] [--dtype f64|f32|mixed]
-                               [--env-a VAR=VAL] [--env-b VAR=VAL]
+                               [--mixed-resolve-iters N] [--env-a VAR=VAL] [--env-b VAR=VAL]
 
 Each library runs in its own child process (STC_LIB selects it); the child writes γ, stat, the iteration
 counts, topic_distribution and the four values of bound() on the same corpus and γ₀ (the no-stats and the
 BOUND kernel instantiations), λ and α after three next() steps, and the launches per kernel family
 (counters()["kernels"], so a changed dispatch shows up), to an .npz, and the parent compares the arrays with
 array_equal.
---dtype goes to LdaHandle as it is, so "mixed" runs the mixed-precision handle on the fp64 corpus.
+--dtype goes to LdaHandle as it is, so "mixed" runs the mixed-precision handle on the fp64 corpus;
+--mixed-resolve-iters is its re-solve threshold (0: the library's 500, which these small corpora never reach, so
+that the fp64 re-solve only runs with a value below their fp32 iteration counts: the printed kernel counts end
+in the re-solves and the re-solved documents).
 Used to show a kernel variant (a build-time switch) or a host-side change leaves every output unchanged
 before timing it.
 """
@@ -23,7 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def child(out, docs, tokens, k, dtype, V):
+def child(out, docs, tokens, k, dtype, V, resolve_iters):
     sys.path.insert(0, os.path.join(ROOT, "spark-text-clustering_amd"))
     import stc
     from stc import synth
@@ -34,7 +37,7 @@ def child(out, docs, tokens, k, dtype, V):
     rng = np.random.default_rng(3)
     lam = rng.gamma(100.0, 0.01, size=(V, k))
     g0 = rng.gamma(100.0, 0.01, size=(docs, k))
-    h = stc.LdaHandle(ctx, k, V, dtype=dtype, mini_batch_fraction=0.05, seed=5)
+    h = stc.LdaHandle(ctx, k, V, dtype=dtype, mini_batch_fraction=0.05, seed=5, mixed_resolve_iters=resolve_iters)
     d = stc.DeviceCsr.upload(ctx, corpus, stc.STC_F32 if dtype == "f32" else stc.STC_F64)
     h.set_corpus(d, docs)
     h.set_topics(lam)
@@ -58,12 +61,13 @@ def main():
     p.add_argument("--k", type=int, default=100)
     p.add_argument("--vocab", type=int, default=1 << 18)
     p.add_argument("--dtype", default="f64")
+    p.add_argument("--mixed-resolve-iters", type=int, default=0, help="--dtype mixed: the re-solve threshold")
     p.add_argument("--child", default=None)
     p.add_argument("--env-a", action="append", default=[], help="VAR=VAL set for the first run only")
     p.add_argument("--env-b", action="append", default=[], help="VAR=VAL set for the second run only")
     a = p.parse_args()
     if a.child:
-        child(a.child, a.docs, a.len, a.k, a.dtype, a.vocab)
+        child(a.child, a.docs, a.len, a.k, a.dtype, a.vocab, a.mixed_resolve_iters)
         return
     outs = []
     with tempfile.TemporaryDirectory() as td:
@@ -72,7 +76,8 @@ def main():
             env = dict(os.environ, STC_LIB=os.path.abspath(lib))
             env.update(kv.split("=", 1) for kv in (a.env_a if i == 0 else a.env_b))
             subprocess.run([sys.executable, __file__, *a.libs, "--docs", str(a.docs), "--len", str(a.len), "--k", str(a.k),
-                            "--vocab", str(a.vocab), "--dtype", a.dtype, "--child", out], env=env, check=True)
+                            "--vocab", str(a.vocab), "--dtype", a.dtype, "--mixed-resolve-iters",
+                            str(a.mixed_resolve_iters), "--child", out], env=env, check=True)
             outs.append(dict(np.load(out)))
     ok = True
     for key in outs[0]:

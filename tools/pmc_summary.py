@@ -31,7 +31,7 @@ sys.path.insert(0, ROOT)
 PHASE = re.compile(r"k_estep|k_sstats|k_fixup|rocprim|fillBuffer|k_part_|k_fill_batch|k_mixed_|k_entry_pairs")
 # bench.py's roofline window (SURVEY §8(d) K6 = gather + scatter): the training E-step launches and the
 # sstats phase after them — the stat clear, the (term, slot) radix sort, k_sstats / k_fixup, logphat and the
-# iteration statistics (HIP events 1 → 3 in lda_online.hip estep_and_stats)
+# iteration statistics (HIP events 1 → 3 in lda_dispatch.hip estep_and_stats)
 WINDOW = re.compile(r"k_estep|k_rows64_long_list|k_sstats|k_fixup|k_logphat|k_iter_stats|fillBuffer"
                     r"|radix_sort_onesweep|k_mixed_|k_entry_pairs")  # (k_mixed_: the mixed mode's fp64 re-solve list and
 # fixup; k_entry_pairs: the fp64 rows path's sstats pairs, built beside the E-step since round 6)
