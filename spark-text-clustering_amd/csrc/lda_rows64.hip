@@ -76,6 +76,26 @@
 #define R64_PA_LAYOUT 1  // 1: the φ-partial rows of a set start at 18·(rl >> 1) + 8·(rl & 1) doubles (stores and
                          // worker reads conflict-free, same footprint); 0: at 10·rl (2-way stores)
 #endif
+// r09: the serial chain of an iteration shortened; no fp operation, operand or order differs under any of the
+// four (DESIGN.md §3 "r09")
+#ifndef R64_DSUM_LATE
+#define R64_DSUM_LATE 1  // 1: Σ|Δγ| (sm.dsum) is read behind Phase A's eθ reads and added at the stop test; 0: read,
+                         // waited for and added right after barrier 2, one LDS round trip ahead of the first eθ read
+#endif
+#ifndef R64_PSI_FIRST
+#define R64_PSI_FIRST 1  // 1: the ψ wave forms γ and the x-only part of the ψ chain first and sums the four ε' sums
+                         // behind it (ψ(Σα + Σcts), the common case's constant, read with the phase's other reads);
+                         // 0: the ε' sum, its test and the dependent read come before γ
+#endif
+#ifndef R64_PSI_EAGER
+#define R64_PSI_EAGER 1  // 1: the ψ chain's γ ≤ 5 values are formed for every lane beside the series (psi64.h
+                         // psi_part_v4 EAGER); 0: the compiler sinks them under exec branches behind it
+#endif
+#ifndef R64_WORKER_LINE
+#define R64_WORKER_LINE 1  // 1: the worker phase without a visible ε' is one predicated sequence and one untaken
+                           // scalar branch, and esum is stored only when its value changes; 0: an if / else per
+                           // lane class, the ballot's else and a store of 0.0 every iteration
+#endif
 #ifndef R64_LONG_OCC
 #define R64_LONG_OCC 1  // long-document kernel workgroups per CU the register budget is cut for
 #endif
@@ -388,6 +408,10 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
   double qr = 0.0;  // worker: r of its row (φ without ε' in qdt)
   qdt = 0.0;
   double dsum = 0.0;
+  [[maybe_unused]] double ds0 = 0.0, ds1 = 0.0;  // R64_DSUM_LATE: sm.dsum as read in Phase A
+  // R64_WORKER_LINE: the wave's esum slot may hold something other than 0.0 (wave-uniform; a new document's slot
+  // holds the last document's value until the first worker phase stores)
+  [[maybe_unused]] uint32_t esnz = 1;
   int it = 0;
   STAMP(0);  // block loads and their barrier
   while (true) {
@@ -434,12 +458,46 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
         }
         if (OVP) __builtin_amdgcn_sched_barrier(0);
       }
+#if R64_DSUM_LATE
+      // Σ|Δγ| of the last update, issued behind the eθ reads (LDS answers a wave in order: nothing here waits for
+      // it) and used at the stop test below.  sm.dsum holds it until the ψ / mirror waves pass the next barrier 1;
+      // at it = 0 the slot is not yet written and the value not used.
+      ds0 = sm.dsum[0];
+      if (npsi == 2) ds1 = sm.dsum[1];
+#endif
 #pragma unroll
       for (int j = 0; j < R; ++j) paw[8 * kPaPitch * j] = acc[j];
     }
     STAMP(1);  // eθ reads, φ FMAs, partial stores
     __builtin_amdgcn_wave_barrier();
     if (R64_PRIO >= 2) __builtin_amdgcn_s_setprio(3);
+#if R64_WORKER_LINE
+    {
+      // φ + ε' of the worker's row.  The other lanes hold −1: what fma(2^53·ε', 2^-53, qdt) gives them (2^53·ε' =
+      // −2^53, qdt = 0), so the compare below is the same lane mask and they need no else branch to form it.
+      double ph = -1.0;
+      if (lane < 8 * R) {
+        const double2* const pr = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(pa) + par_o);
+        const double2 x0 = pr[0], x1 = pr[1], x2 = pr[2], x3 = pr[3];
+        qdt = ((x0.x + x0.y) + (x1.x + x1.y)) + ((x2.x + x2.y) + (x3.x + x3.y));
+        ph = fma(qe2, 0x1p-53, qdt);
+        qr = qc * rcp_nr(ph);
+        sm.rrow[w][lane] = qr;
+      }
+      // ε' visible at fp64 resolution (2^53·ε' ≥ φ) in some row of the wave: rare, and then in every iteration
+      // of the document.  The common path takes neither branch and stores nothing: the slot holds 0.0 from the
+      // document's first worker phase (esnz starts true) or from the phase after the last visible one.
+      const uint64_t vm = __builtin_amdgcn_ballot_w64(qe2 >= ph);
+      if (__builtin_expect(((uint32_t)vm | (uint32_t)(vm >> 32) | esnz) != 0, 0)) {
+        double e = 0.0;
+        if (vm != 0) e = wave_sum_d(lane < 8 * R ? qr * (qe2 * 0x1p-53) : 0.0);
+        int l0 = lane;  // (the lane test formed here: see the mirror wave's store below)
+        asm volatile("" : "+v"(l0));
+        if (l0 == 0) *esw = e;
+        esnz = __builtin_amdgcn_readfirstlane(vm != 0);  // (kept in an SGPR: the test above is scalar code)
+      }
+    }
+#else
     if (lane < 8 * R) {
       const double2* const pr = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(pa) + par_o);
       const double2 x0 = pr[0], x1 = pr[1], x2 = pr[2], x3 = pr[3];
@@ -463,6 +521,7 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
     } else if (lane == 0) {
       *esw = 0.0;
     }
+#endif
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < R; ++j) rr[j] = sm.rrow[w][8 * j + rl];
@@ -470,7 +529,13 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
     STAMP(2);  // worker sums, r, ε' ballot, r reads
     // Spark: while (meanGammaChange > 1e-3); dsum is block-uniform (every wave adds the same LDS
     // values in the same order)
+#if R64_DSUM_LATE
+    // (added for it = 0 too, and tested without short circuits: a skipped add is a scalar branch on the chain)
+    dsum = npsi == 2 ? ds0 + ds1 : ds0;
+    if (((int)(it > 0) & (int)(dsum <= a.stop_thr)) | (int)(it >= a.max_iter)) break;
+#else
     if ((it > 0 && dsum <= a.stop_thr) || it >= a.max_iter) break;
+#endif
 
     // Phase B: s partials over the lane's R rows, one row lane's slot per topic
 #if R64_SB_LDS
@@ -540,13 +605,31 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
         const double2 ap = *reinterpret_cast<const double2*>(&sm.apc[tt][0]);  // α_t, ψc_t
         const double2 e01 = *reinterpret_cast<const double2*>(&sm.esum[0]);
         const double2 e23 = *reinterpret_cast<const double2*>(&sm.esum[2]);
+#if R64_PSI_FIRST
+        const double cflat = sm.ac[2];  // ψ(Σα + Σcts): ψ(Σγ') without a visible ε'
+        const double s = (x0.x + x0.y) + (x1.x + x1.y);
+        const double gn = fma(eo, s, ap.x);  // γ ← eθ ⊙ s + α
+        dg = fabs(gn - g);
+        sm.gam[tt] = gn;
+        // what the chain needs of γ alone, ahead of the ε' sums: ψ(Σγ') enters only where it is subtracted
+        double y;
+        const double zt = psi_part_v4<R64_RCP_NR, R64_PSI_EAGER != 0>(gn, y);
+        __builtin_amdgcn_sched_barrier(0);  // (the scheduler put the ε' sum, its test and branch first)
+        const double et = (e01.x + e01.y) + (e23.x + e23.y);
+        double csn = cflat;
+        // (inlined by force: marked unlikely, the compiler left a call here, and a call in the loop costs the
+        // kernel the callee-clobbered SGPRs around it)
+        if (__builtin_expect(et != 0.0, 0)) [[clang::always_inline]] csn = digamma_fast_d(sm.ac[0] + sm.ac[1] - et);
+        const double en = y * exp_vk(zt - (csn + ap.y), expk);
+#else
         const double s = (x0.x + x0.y) + (x1.x + x1.y);
         const double et = (e01.x + e01.y) + (e23.x + e23.y);
         const double csn = et != 0.0 ? digamma_fast_d(sm.ac[0] + sm.ac[1] - et) : sm.ac[2];
         const double gn = fma(eo, s, ap.x);  // γ ← eθ ⊙ s + α
         dg = fabs(gn - g);
         sm.gam[tt] = gn;
-        const double en = exp_digamma_minus_v4<R64_RCP_NR>(gn, csn + ap.y, expk);
+        const double en = exp_digamma_minus_v4<R64_RCP_NR, R64_PSI_EAGER != 0>(gn, csn + ap.y, expk);
+#endif
         sm.eth[ttl][ttp] = en;
         gm = gn;
         em = en;
@@ -570,11 +653,21 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
         gm = gn;  // (its eθ: the ψ wave's, from LDS, when this wave is next the ψ wave)
       }
       const double d = wave_sum_d(dg);
+#if R64_WORKER_LINE
+      // (the lane test formed here, one v_cmp off the chain: as a lane mask held across the loop it was the value
+      // the allocator spilled, two v_readlane at each use)
+      int l0 = lane;
+      asm volatile("" : "+v"(l0));
+      if (l0 == 0) sm.dsum[pw] = d;
+#else
       if (lane == 0) sm.dsum[pw] = d;
+#endif
     }
     STAMP(psi ? 5 : 8);  // ψ phase (ψ waves; non-ψ waves: nothing)
     __syncthreads();  // (2) eθ, γ, Σ|Δγ| published
+#if !R64_DSUM_LATE
     dsum = npsi == 2 ? sm.dsum[0] + sm.dsum[1] : sm.dsum[0];
+#endif
     STAMP(psi ? 6 : 9);  // barrier 2 (ψ waves / the others)
     ++it;
   }

@@ -165,8 +165,16 @@ __device__ __forceinline__ double exp_vk(double z, const PsiExpK& C) {
   o = __builtin_fma(o, r2, 1.0);
   return __builtin_ldexp(__builtin_fma(r, o, e), (int)fmax(n, -1100.0));  // n < -1100: 0
 }
-template <int RCP_STEPS>
-__device__ __forceinline__ double exp_digamma_minus_v4(double x, double cst, const PsiExpK& C) {
+// v4 in two parts, so a caller whose cst arrives late can start the first before it has cst:
+//   psi_part_v4: ψ(x) − ln y, and y (x, or x + 6 where x ≤ 5): everything that needs x alone;
+//   exp_digamma_minus_v4(x, cst) = y · exp((ψ(x) − ln y) − cst).
+// EAGER: the x ≤ 5 values (x + 6, the recurrence terms c, the truncation fix) are laundered, so they are computed
+// for every lane beside the series and selected, as the source says.  Left alone the compiler sinks them under
+// `if (any lane has x ≤ 5)` exec branches behind the series; where some lane of the wave almost always has
+// x ≤ 5 (the rows E-step's γ), the branch buys nothing and its ≈ 17 dependent steps run after the series instead
+// of beside it.  Same instructions on the same operands either way.
+template <int RCP_STEPS, bool EAGER>
+__device__ __forceinline__ double psi_part_v4(double x, double& y_out) {
   const bool sh = x <= 5.0;
   const double xs = sh ? x : 1.0;
   const double u = xs * add_s(xs, 5.0);
@@ -175,9 +183,19 @@ __device__ __forceinline__ double exp_digamma_minus_v4(double x, double cst, con
   const double iq = rcp_n<RCP_STEPS>(den);
   double c = num * iq;
   c = fma(fma(-den, c, num), iq, c);
-  const double y = sh ? add_s(x, 6.0) : x;
+  double x6 = 0.0;
+  if (EAGER) {
+    x6 = add_s(x, 6.0);
+    asm volatile("" : "+v"(x6));
+  }
+  const double y = sh ? (EAGER ? x6 : add_s(x, 6.0)) : x;
   const double iy = rcp_n<RCP_STEPS>(y);
   const double f = iy * iy;
+  double tf = 0.0;
+  if (EAGER) {
+    tf = trunc_fix_pk(f, xs);
+    asm volatile("" : "+v"(c), "+v"(tf));
+  }
   double t = add_s(mul_s(f, 3617.0 / 8160.0), -1.0 / 12.0);
   t = fma_s(t, f, 691.0 / 32760.0);
   t = fma_s(t, f, -1.0 / 132.0);
@@ -185,8 +203,14 @@ __device__ __forceinline__ double exp_digamma_minus_v4(double x, double cst, con
   t = fma_s(t, f, -1.0 / 252.0);
   t = fma_s(t, f, 1.0 / 120.0);
   t = fma_s(t, f, -1.0 / 12.0) * f;
-  const double shift = sh ? trunc_fix_pk(f, xs) - c : 0.0;
-  const double z = (fma(-0.5, iy, shift) + t) - cst;
+  const double shift = sh ? (EAGER ? tf : trunc_fix_pk(f, xs)) - c : 0.0;
+  y_out = y;
+  return fma(-0.5, iy, shift) + t;
+}
+template <int RCP_STEPS, bool EAGER = false>
+__device__ __forceinline__ double exp_digamma_minus_v4(double x, double cst, const PsiExpK& C) {
+  double y;
+  const double z = psi_part_v4<RCP_STEPS, EAGER>(x, y) - cst;
   return y * exp_vk(z, C);
 }
 
@@ -197,5 +221,7 @@ using psi64::psik_fill;
 using psi64::PsiExpK;
 using psi64::psi_expk_load;
 using psi64::exp_digamma_minus_v4;
+using psi64::psi_part_v4;
+using psi64::exp_vk;
 }  // namespace lda
 }  // namespace stc
