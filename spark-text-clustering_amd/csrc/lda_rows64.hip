@@ -96,6 +96,13 @@
                            // scalar branch, and esum is stored only when its value changes; 0: an if / else per
                            // lane class, the ballot's else and a store of 0.0 every iteration
 #endif
+// r10: Phase A of the six-row-set loop (R > RG: a row set in LDS); no fp operation, operand or order differs, and
+// the R ≤ 5 loops are the same instructions (DESIGN.md §3 "r10")
+#ifndef R64_OVF_AHEAD
+#define R64_OVF_AHEAD 1  // 1: the LDS row set's B values are read one eθ pair ahead of their FMAs and the steps are
+                         // fenced (the form R64_SB_LDS already had); 0: each read is issued behind the wait for the
+                         // last one, ⌈KL/2⌉ LDS round trips in series inside Phase A
+#endif
 #ifndef R64_LONG_OCC
 #define R64_LONG_OCC 1  // long-document kernel workgroups per CU the register budget is cut for
 #endif
@@ -424,7 +431,9 @@ __device__ __forceinline__ int rows64_iterate(const EStepArgs<double>& a, RLds<S
       // With a row set in LDS the step's eθ pair and B values are read one step ahead and the steps are
       // fenced: left to itself the scheduler reads all KL of both up front, 54 VGPRs beside the block's
       // 26·RG, and the document context held across the loop spills.
-      constexpr bool OVP = R64_SB_LDS != 0 && R > RG;
+      // In the in-register build (R64_SB_LDS = 0) the unfenced loop reads one step at a time instead, each
+      // ds_read2st64_b64 behind s_waitcnt lgkmcnt(0) for the last: R64_OVF_AHEAD gives it the same fenced form.
+      constexpr bool OVP = (R64_SB_LDS != 0 || R64_OVF_AHEAD != 0) && R > RG;
       constexpr int NO = OVP ? 2 * (R - RG) : 1;
       double2 en = make_double2(0.0, 0.0);
       double on[NO] = {};

@@ -71,6 +71,12 @@ def main():
          "max": float(rel[(it64 > lo) & (it64 <= hi)].max()) if np.any((it64 > lo) & (it64 <= hi)) else None}
         for lo, hi in zip(edges[:-1], edges[1:])]
     out["iters_equal_f32_f64"] = float((it32 == it64).mean())
+    # per row-set count ⌈nnz/32⌉ (the fp64 rows E-step's loop specialisation): documents and document-iterations
+    indptr = np.asarray(corpus.indptr)
+    rs = ((indptr[1:] - indptr[:-1])[ids] + 31) // 32
+    out["mean_row_sets"] = float(rs.mean())
+    out["by_row_sets"] = {str(int(r)): {"docs": float((rs == r).mean()), "iteration_share": float(it64[rs == r].sum() / tot),
+                                        "mean_iters": float(it64[rs == r].mean())} for r in np.unique(rs)}
     print(json.dumps(out), flush=True)
 
 
