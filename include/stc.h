@@ -32,6 +32,11 @@
  *   stc_lda_describe            ldaModel.describeTopics(maxTermsPerTopic) — LDAClustering.scala:81,
  *                               LDALoader.scala:66
  *   stc_lda_topic_distribution  toLocal.topicDistribution(tf) — LDALoader.scala:108
+ *   stc_lda_score, stc_score_*  the report LDALoader writes from those proportions: the main topic —
+ *                               LDALoader.scala:131-140, the books of each topic — :142-149, and the
+ *                               ranked lists a report adds (topTopicsPerDocument / topDocumentsPerTopic)
+ *   stc_lda_important_terms     "Book most important words" — LDALoader.scala:86-94 (the book's tokens by
+ *                               count), :154-163 (the first 100 ∩ the main topic's 300 terms, the first 10)
  *   stc_lda_bound               [U] LocalLDAModel.logLikelihood / logPerplexity
  *   stc_em_*                    [U] EMLDAOptimizer, the reference's default optimizer ("em", Params.scala:9) —
  *                               LDAClustering.scala:41; stc_em_log_likelihood is
@@ -640,6 +645,71 @@ int stc_em_group_topic_assignments(stc_em_group* g, int64_t* indptr_out, int32_t
   int stc_em_group_top_documents(stc_em_group* g, int64_t max_docs, int64_t* n_out, int64_t* row_out,
                                  double* weight_out);
   int stc_em_group_top_topics(stc_em_group* g, int32_t n_topics, int32_t* idx_out, double* weight_out);
+
+/* ---- Document scores (the clustering report of LDALoader.scala:86-94, 131-163) ------------------
+ * A set of documents is scored once; the score stays on the device and answers what a clustering report
+ * asks — each document's main topic, the documents of each topic, ranked lists, the words that tie a document
+ * to its topic — without γ crossing to the host.
+ * An stc_dscore holds γ (rows×k, fp64; a row marked empty is stored as 0) and per row
+ *   rowsum[r] = ((|γ[r][0]| + |γ[r][1]|) + …) + |γ[r][k−1]|, added sequentially in ascending j, −1 for an empty row;
+ * θ[r][j] = γ[r][j] / rowsum[r] (γ[r][j] itself where the sum is 0, so an empty row's θ is 0).
+ *   stc_lda_score         exactly the E-step of stc_lda_topic_distribution (same arguments, same γ₀ keys, an
+ *                         STC_MIXED handle infers in fp64) with γ widened to fp64 and kept; a row is empty iff it
+ *                         has no entries.  Keeps no reference to `docs`.
+ *   stc_score_from_gamma  the same object from a host matrix (the EM model's doc_topics, planted values): gamma
+ *                         rows×k, every entry finite and >= 0 (else STC_ERR_INVALID_ARG); empty[r] != 0 marks row r
+ *                         empty (NULL: none is).  2 <= k <= 4096.
+ *   topic_distribution    out rows×k = θ: bitwise what stc_lda_topic_distribution writes for the same call.
+ *   main_topics           the topic with the largest θ, among equal maxima the LARGEST index (LDALoader.scala:136
+ *                         updates on `mainTopicWeight <= weight`); weight_out = that θ (bitwise γ / rowsum).  An
+ *                         empty row: topic −1, weight 0 (the reference drops empty documents).  count_out[t] = the
+ *                         rows whose main topic is t.  Any k the online handle accepts (<= 4096).
+ *   members               the non-empty rows grouped by main topic, ascending inside a topic: indptr_out int64[k+1]
+ *                         (indptr_out[t+1] − indptr_out[t] = count[t]), rows_out int64[nonempty] (stc_score_shape).
+ *                         Integer counters and a stable integer sort only.
+ *   top_topics            stc_em_top_topics' contract over (γ, rowsum): idx_out int32[rows×N], weight_out
+ *                         double[rows×N], N = min(n_topics, k), ties by ascending topic, an empty row yields topics
+ *                         0 … N−1 with weight 0.  k <= 1024 (above: STC_ERR_INVALID_ARG).
+ *   top_documents         stc_em_top_documents' contract: per topic the non-empty rows with the largest θ, ties by
+ *                         ascending row; cap = min(max_docs, rows) is the outputs' stride, row_out int64[k×cap],
+ *                         weight_out double[k×cap], *n_out = N = min(max_docs, nonempty).
+ *   stc_lda_important_terms  per row d of `docs` (the matrix that was scored: the same rows, V columns):
+ *                         t_d = row d's main topic (topic_of == NULL) or topic_of[d] (−1: the row yields nothing; any
+ *                         other value outside 0 … k−1: STC_ERR_INVALID_ARG);
+ *                         L_d = the first min(doc_terms, nnz_d) entries of the row by (value descending, term index
+ *                         ascending) — values widened to fp64, −0 read as 0, negative values below positive ones,
+ *                         NaN unpinned; ties rank by term index whatever the order of the row's entries;
+ *                         S_t = the min(topic_terms, V) terms with the largest λ[w][t], ties by ascending term
+ *                         (stc_lda_describe's order; no V·k < 2^31 limit here);
+ *                         the result = the first max_out entries of L_d whose term is in S_{t_d}, in L_d's order
+ *                         (Scala's slice(0, 100).intersect(topicVocab).slice(0, 10); LDALoader's numbers are
+ *                         doc_terms 100, topic_terms 300, max_out 10).  idx_out int32[rows×max_out] and value_out
+ *                         double[rows×max_out] (unused slots: −1 and 0), n_out int32[rows].  All three counts >= 1,
+ *                         doc_terms <= 1024.
+ * Any output pointer may be NULL.  A score belongs to its stc_ctx as an stc_dcsr does: a handle of another
+ * context returns STC_ERR_INVALID_ARG.  Single device: a context connected to other ranks returns STC_ERR_STATE,
+ * as does an LDA handle without topics.  Every call waits for queued work.  Results are bitwise reproducible: a
+ * result depends on the scores (and for the terms on `docs` and λ) alone; no float atomics anywhere. */
+typedef struct stc_dscore stc_dscore;
+  int stc_lda_score(stc_lda* lda, const stc_dcsr* docs, uint64_t gamma_seed, int64_t doc_id_base,
+                    const double* gamma0, stc_dscore** out);
+  int stc_score_from_gamma(stc_ctx* ctx, const double* gamma, const uint8_t* empty, int64_t rows, int32_t k,
+                           stc_dscore** out);
+  /* frees the device memory (valid after stc_destroy of the context) */
+  int stc_score_free(stc_dscore* score);
+  int stc_score_shape(const stc_dscore* score, int64_t* rows, int32_t* k, int64_t* nonempty);
+  int stc_score_topic_distribution(stc_ctx* ctx, const stc_dscore* score, double* out /* rows×k */);
+  int stc_score_main_topics(stc_ctx* ctx, const stc_dscore* score, int32_t* topic_out /* rows */,
+                            double* weight_out /* rows */, int64_t* count_out /* k */);
+  int stc_score_members(stc_ctx* ctx, const stc_dscore* score, int64_t* indptr_out /* k+1 */,
+                        int64_t* rows_out /* nonempty */);
+  int stc_score_top_topics(stc_ctx* ctx, const stc_dscore* score, int32_t n_topics, int32_t* idx_out,
+                           double* weight_out);
+  int stc_score_top_documents(stc_ctx* ctx, const stc_dscore* score, int64_t max_docs, int64_t* n_out,
+                              int64_t* row_out, double* weight_out);
+  int stc_lda_important_terms(stc_lda* lda, const stc_dcsr* docs, const stc_dscore* score, const int32_t* topic_of,
+                              int32_t doc_terms, int32_t topic_terms, int32_t max_out, int32_t* idx_out,
+                              double* value_out, int32_t* n_out);
 
 #ifdef __cplusplus
 }

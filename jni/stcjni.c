@@ -1426,3 +1426,141 @@ JNIEXPORT void JNICALL FN(emGroupTopTopics)(JNIEnv* env, jclass c, jlong g, jint
   if (emg_shape(env, g, s)) return;
   em_top_topics_any(env, s, EMG(g), 1, n_topics, idx, weight, "emGroupTopTopics");
 }
+
+/* ---- document scores (stc_lda_score, stc_score_*, stc_lda_important_terms) ------------------------------ */
+#define SCORE(h) ((stc_dscore*)(intptr_t)(h))
+/* s = {rows, k, nonempty} */
+static int score_shape(JNIEnv* env, jlong score, int64_t s[3]) {
+  int32_t k = 0;
+  if (check(env, stc_score_shape(SCORE(score), &s[0], &k, &s[2]))) return 1;
+  s[1] = k;
+  return 0;
+}
+
+JNIEXPORT jlong JNICALL FN(ldaScore)(JNIEnv* env, jclass c, jlong lda, jlong dcsr, jlong gamma_seed, jlong doc_id_base,
+                                     jdoubleArray gamma0) {
+  int64_t k = 0, V = 0, rows = 0, cols = 0, nnz = 0;
+  stc_dscore* out = NULL;
+  if (lda_shape(env, lda, &k, &V) || csr_shape(env, dcsr, &rows, &cols, &nnz) || NEED(gamma0, rows * k, "ldaScore gamma0"))
+    return 0;
+  jdouble* g = PIN(jdouble, Double, gamma0);
+  int st = stc_lda_score(LDA(lda), CSR(dcsr), (uint64_t)gamma_seed, doc_id_base, g, &out);
+  UNPIN(Double, gamma0, g, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT jlong JNICALL FN(scoreFromGamma)(JNIEnv* env, jclass c, jlong ctx, jdoubleArray gamma, jbyteArray empty,
+                                           jlong rows, jint k) {
+  stc_dscore* out = NULL;
+  if (rows < 0 || k < 0 || NEED(gamma, rows * k, "scoreFromGamma gamma") || NEED(empty, rows, "scoreFromGamma empty"))
+    return 0;
+  jdouble* g = PIN(jdouble, Double, gamma);
+  jbyte* e = PIN(jbyte, Byte, empty);
+  int st = stc_score_from_gamma(CTX(ctx), g, (const uint8_t*)e, rows, k, &out);
+  UNPIN(Byte, empty, e, JNI_ABORT);
+  UNPIN(Double, gamma, g, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)(intptr_t)out;
+}
+
+JNIEXPORT void JNICALL FN(scoreFree)(JNIEnv* env, jclass c, jlong score) { check(env, stc_score_free(SCORE(score))); }
+
+/* {rows, k, nonempty} */
+JNIEXPORT jlongArray JNICALL FN(scoreShape)(JNIEnv* env, jclass c, jlong score) {
+  int64_t s[3] = {0, 0, 0};
+  if (score_shape(env, score, s)) return NULL;
+  jlongArray out = (*env)->NewLongArray(env, 3);
+  if (out) (*env)->SetLongArrayRegion(env, out, 0, 3, (const jlong*)s);
+  return out;
+}
+
+JNIEXPORT void JNICALL FN(scoreTopicDistribution)(JNIEnv* env, jclass c, jlong ctx, jlong score, jdoubleArray out) {
+  int64_t s[3] = {0, 0, 0};
+  if (score_shape(env, score, s) || NEED(out, s[0] * s[1], "scoreTopicDistribution out")) return;
+  jdouble* o = PIN(jdouble, Double, out);
+  int st = stc_score_topic_distribution(CTX(ctx), SCORE(score), o);
+  UNPIN(Double, out, o, 0);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL FN(scoreMainTopics)(JNIEnv* env, jclass c, jlong ctx, jlong score, jintArray topic,
+                                           jdoubleArray weight, jlongArray count) {
+  int64_t s[3] = {0, 0, 0};
+  if (score_shape(env, score, s) || NEED(topic, s[0], "scoreMainTopics topic") ||
+      NEED(weight, s[0], "scoreMainTopics weight") || NEED(count, s[1], "scoreMainTopics count"))
+    return;
+  jint* t = PIN(jint, Int, topic);
+  jdouble* w = PIN(jdouble, Double, weight);
+  jlong* n = PIN(jlong, Long, count);
+  int st = stc_score_main_topics(CTX(ctx), SCORE(score), (int32_t*)t, w, (int64_t*)n);
+  UNPIN(Long, count, n, 0);
+  UNPIN(Double, weight, w, 0);
+  UNPIN(Int, topic, t, 0);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL FN(scoreMembers)(JNIEnv* env, jclass c, jlong ctx, jlong score, jlongArray indptr,
+                                        jlongArray rows) {
+  int64_t s[3] = {0, 0, 0};
+  if (score_shape(env, score, s) || NEED(indptr, s[1] + 1, "scoreMembers indptr") || NEED(rows, s[2], "scoreMembers rows"))
+    return;
+  jlong* ip = PIN(jlong, Long, indptr);
+  jlong* r = PIN(jlong, Long, rows);
+  int st = stc_score_members(CTX(ctx), SCORE(score), (int64_t*)ip, (int64_t*)r);
+  UNPIN(Long, rows, r, 0);
+  UNPIN(Long, indptr, ip, 0);
+  check(env, st);
+}
+
+JNIEXPORT void JNICALL FN(scoreTopTopics)(JNIEnv* env, jclass c, jlong ctx, jlong score, jint n_topics, jintArray idx,
+                                          jdoubleArray weight) {
+  int64_t s[3] = {0, 0, 0};
+  if (score_shape(env, score, s)) return;
+  const int64_t N = n_topics < s[1] ? (n_topics > 0 ? n_topics : 0) : s[1];
+  if (NEED(idx, s[0] * N, "scoreTopTopics idx") || NEED(weight, s[0] * N, "scoreTopTopics weight")) return;
+  jint* ix = PIN(jint, Int, idx);
+  jdouble* w = PIN(jdouble, Double, weight);
+  int st = stc_score_top_topics(CTX(ctx), SCORE(score), n_topics, (int32_t*)ix, w);
+  UNPIN(Double, weight, w, 0);
+  UNPIN(Int, idx, ix, 0);
+  check(env, st);
+}
+
+/* returns N; rows / weight k × min(maxDocs, rows) */
+JNIEXPORT jlong JNICALL FN(scoreTopDocuments)(JNIEnv* env, jclass c, jlong ctx, jlong score, jlong max_docs,
+                                              jlongArray rows, jdoubleArray weight) {
+  int64_t s[3] = {0, 0, 0}, n = 0;
+  if (score_shape(env, score, s)) return 0;
+  const int64_t cap = max_docs < s[0] ? (max_docs > 0 ? max_docs : 0) : s[0];
+  if (NEED(rows, s[1] * cap, "scoreTopDocuments rows") || NEED(weight, s[1] * cap, "scoreTopDocuments weight")) return 0;
+  jlong* r = PIN(jlong, Long, rows);
+  jdouble* w = PIN(jdouble, Double, weight);
+  int st = stc_score_top_documents(CTX(ctx), SCORE(score), max_docs, &n, (int64_t*)r, w);
+  UNPIN(Double, weight, w, 0);
+  UNPIN(Long, rows, r, 0);
+  if (check(env, st)) return 0;
+  return (jlong)n;
+}
+
+JNIEXPORT void JNICALL FN(ldaImportantTerms)(JNIEnv* env, jclass c, jlong lda, jlong dcsr, jlong score, jintArray topic_of,
+                                             jint doc_terms, jint topic_terms, jint max_out, jintArray idx,
+                                             jdoubleArray value, jintArray n_out) {
+  int64_t s[3] = {0, 0, 0};
+  if (score_shape(env, score, s)) return;
+  const int64_t width = max_out > 0 ? max_out : 0;
+  if (NEED(topic_of, s[0], "ldaImportantTerms topicOf") || NEED(idx, s[0] * width, "ldaImportantTerms idx") ||
+      NEED(value, s[0] * width, "ldaImportantTerms value") || NEED(n_out, s[0], "ldaImportantTerms nOut"))
+    return;
+  jint* t = PIN(jint, Int, topic_of);
+  jint* ix = PIN(jint, Int, idx);
+  jdouble* v = PIN(jdouble, Double, value);
+  jint* n = PIN(jint, Int, n_out);
+  int st = stc_lda_important_terms(LDA(lda), CSR(dcsr), SCORE(score), (const int32_t*)t, doc_terms, topic_terms, max_out,
+                                   (int32_t*)ix, v, (int32_t*)n);
+  UNPIN(Int, n_out, n, 0);
+  UNPIN(Double, value, v, 0);
+  UNPIN(Int, idx, ix, 0);
+  UNPIN(Int, topic_of, t, JNI_ABORT);
+  check(env, st);
+}

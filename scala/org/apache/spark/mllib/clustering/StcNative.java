@@ -264,4 +264,30 @@ public final class StcNative {
   public static native void emGroupDescribe(long emGroup, int maxTerms, int[] idx, double[] weight);
   public static native long emGroupTopDocuments(long emGroup, long maxDocs, long[] rows, double[] weight);
   public static native void emGroupTopTopics(long emGroup, int nTopics, int[] idx, double[] weight);
+
+  // ---- document scores (stc_lda_score / stc_score_*: the report of LDALoader.scala:86-94, 131-163)
+  /** ldaTopicDistribution's E-step with γ kept on the GPU; the score belongs to the LDA handle's context */
+  public static native long ldaScore(long lda, long dcsr, long gammaSeed, long docIdBase, double[] gamma0);
+  /** the same object from a host matrix rows×k (finite, >= 0); empty[r] != 0 marks row r empty (nullable) */
+  public static native long scoreFromGamma(long ctx, double[] gamma, byte[] empty, long rows, int k);
+  public static native void scoreFree(long score);
+  /** {rows, k, nonEmpty} */
+  public static native long[] scoreShape(long score);
+  /** out rows×k: bitwise ldaTopicDistribution's of the same call */
+  public static native void scoreTopicDistribution(long ctx, long score, double[] out);
+  /** topic[rows] (the largest θ, among equal maxima the largest index; −1 for an empty row), weight[rows], count[k];
+   *  every array nullable */
+  public static native void scoreMainTopics(long ctx, long score, int[] topic, double[] weight, long[] count);
+  /** the non-empty rows grouped by main topic, ascending inside a topic: indptr[k + 1], rows[nonEmpty] */
+  public static native void scoreMembers(long ctx, long score, long[] indptr, long[] rows);
+  /** emTopTopics' contract over the score: idx / weight rows × min(nTopics, k); k <= 1024 */
+  public static native void scoreTopTopics(long ctx, long score, int nTopics, int[] idx, double[] weight);
+  /** emTopDocuments' contract: rows / weight k × min(maxDocs, rows); returns N = min(maxDocs, nonEmpty) */
+  public static native long scoreTopDocuments(long ctx, long score, long maxDocs, long[] rows, double[] weight);
+  /** "Book most important words": per row of dcsr (the matrix that was scored) the first maxOut of its docTerms
+   *  largest entries (value descending, term ascending) whose term is among the topicTerms heaviest terms of the
+   *  row's main topic (topicOf[rows], nullable: of that topic; −1 skips the row).  idx / value rows × maxOut
+   *  (unused slots −1 / 0), nOut[rows].  LDALoader's numbers: 100, 300, 10 */
+  public static native void ldaImportantTerms(long lda, long dcsr, long score, int[] topicOf, int docTerms,
+                                              int topicTerms, int maxOut, int[] idx, double[] value, int[] nOut);
 }

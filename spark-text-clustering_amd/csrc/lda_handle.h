@@ -1,6 +1,7 @@
 // lda_handle.h — struct stc_lda and what the three translation units behind the stc_lda_* entry points share:
 // lda_dispatch.hip (which kernel runs these slots), lda_train.hip (a training step around the E-step) and
-// lda_online.hip (the C ABI and the readers).  Private to those three; no kernel file includes it.
+// lda_online.hip (the C ABI and the readers).  Private to those three and to lda_score.hip (the document scores,
+// which read γ, λ and the handle's shape); no kernel file includes it.
 #pragma once
 
 #include <type_traits>
@@ -219,5 +220,11 @@ template <typename T>
 void step_ids(stc_lda& L, const int64_t* ids, int64_t n, const double* gamma0, stc_step_stats* st);
 template <typename T>
 void next_impl(stc_lda& L, stc_step_stats* st);
+
+
+// ---- lda_online.hip ----
+// the E-step of stc_lda_topic_distribution over `docs`; returns γ on the device (rows×k of by_infer_type's type,
+// the handle's mb.gamma: valid until the handle's next call), enqueued on the context's stream
+const void* score_gamma(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const double* gamma0);
 
 }  // namespace stc::online

@@ -59,7 +59,7 @@ void estep_only(stc_lda& L, const int64_t* ids, int64_t n, const double* gamma0,
 // the E-step over other documents than the training corpus (so no row order), keyed by doc_id_base + row
 template <typename T>
 void infer_impl(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const double* gamma0,
-                bool bound, double* gamma_out, double* out4 /* corpus, tokens */) {
+                bool bound, double* gamma_out, double* out4 /* corpus, tokens */, bool keep_gamma = false) {
   if (!L.model.has_topics) throw Error(STC_ERR_STATE, "no topics: call stc_lda_init_random or stc_lda_set_topics");
   STC_REQUIRE(docs.cols == L.V, "document vectors must have vocab_size columns");
   STC_REQUIRE(docs.dtype == corpus_dtype(L), "document CSR dtype must match the LDA dtype (STC_F64 for STC_MIXED)");
@@ -84,7 +84,7 @@ void infer_impl(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const
   a.key_mode = 1;
   a.doc_id_base = base;
   a.r = B.r.as<T>();
-  a.gamma = gamma_out ? B.gamma.as<T>() : nullptr;
+  a.gamma = (gamma_out || keep_gamma) ? B.gamma.as<T>() : nullptr;  // keep_gamma: γ stays in mb.gamma (score_gamma)
   a.iters = B.iters.as<int32_t>();
   a.bound = bound ? B.bound.as<double>() : nullptr;
   a.lam = bound && !L.model.lam_stale ? L.model.lam.as<double>() : nullptr;
@@ -135,6 +135,14 @@ void topics_part(stc_lda& L, double* elem_part, double* norm_part) {
 }
 
 }  // namespace
+
+// lda_score.hip's E-step: stc_lda_topic_distribution's, with γ (rows×k of the infer type) left in mb.gamma
+const void* stc::online::score_gamma(stc_lda& L, const DCsr& docs, uint64_t seed, int64_t base, const double* gamma0) {
+  by_infer_type(L, [&](auto t) {
+    infer_impl<decltype(t)>(L, docs, seed, base, gamma0, false, nullptr, nullptr, true);
+  });
+  return L.mb.gamma.p;
+}
 
 extern "C" {
 

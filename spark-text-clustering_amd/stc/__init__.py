@@ -7,7 +7,7 @@ from ._lib import (STC_ERR_HIP, STC_ERR_INVALID_ARG, STC_ERR_OOM, STC_ERR_RCCL, 
                    STC_HASH_SPARK24, STC_HASH_STANDARD, STC_LAYOUT_KV, STC_LAYOUT_VK, StcError, StcIllegalArgument,
                    load)
 from . import io
-from .clustering import (LDA, ML_LDA_DEFAULT_SEED, DistributedLDAModel, EmGroup, EmHandle, EMLDAOptimizer, LdaGroup,
+from .clustering import (LDA, ML_LDA_DEFAULT_SEED, DistributedLDAModel, DocumentScores, EmGroup, EmHandle, EMLDAOptimizer, LdaGroup,
                          LdaHandle, LDAModel, MllibLDA, OnlineLDAOptimizer, em_concentrations,
                          reference_mini_batch_fraction)
 from .core import Context, CsrMatrix, DeviceCsr
@@ -18,7 +18,7 @@ from .token_stages import NGram, StopWordsRemover
 
 __all__ = [
     "Context", "CsrMatrix", "DeviceCsr", "CountVectorizer", "CountVectorizerModel", "HashingTF", "IDF", "IDFModel", "Tokenizer", "DeviceTokens", "TextPreprocessor", "StopWordsRemover", "NGram", "PorterStemmer", "DEFAULT_STRIP_CHARS", "encode_texts", "encode_tokens", "LDA",
-    "LDAModel", "DistributedLDAModel", "LdaGroup", "LdaHandle", "EmHandle", "EmGroup", "io", "MllibLDA", "OnlineLDAOptimizer",
+    "LDAModel", "DistributedLDAModel", "DocumentScores", "LdaGroup", "LdaHandle", "EmHandle", "EmGroup", "io", "MllibLDA", "OnlineLDAOptimizer",
     "EMLDAOptimizer", "em_concentrations", "ML_LDA_DEFAULT_SEED", "reference_mini_batch_fraction", "StcError", "StcIllegalArgument", "load", "STC_F32", "STC_F64", "STC_MIXED",
     "STC_HASH_STANDARD", "STC_HASH_SPARK24", "STC_LAYOUT_VK", "STC_LAYOUT_KV", "STC_ERR_INVALID_ARG", "STC_ERR_HIP",
     "STC_ERR_RCCL", "STC_ERR_OOM", "STC_ERR_STATE",

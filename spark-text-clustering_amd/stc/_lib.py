@@ -197,6 +197,16 @@ SIGNATURES = {
     "stc_em_group_describe": (_int, [_p, _i32, _pi32, _pdbl]),
     "stc_em_group_top_documents": (_int, [_p, _i64, _pi64, _pi64, _pdbl]),
     "stc_em_group_top_topics": (_int, [_p, _i32, _pi32, _pdbl]),
+    "stc_lda_score": (_int, [_p, _p, _u64, _i64, _pdbl, C.POINTER(_p)]),
+    "stc_score_from_gamma": (_int, [_p, _pdbl, _pu8, _i64, _i32, C.POINTER(_p)]),
+    "stc_score_free": (_int, [_p]),
+    "stc_score_shape": (_int, [_p, _pi64, _pi32, _pi64]),
+    "stc_score_topic_distribution": (_int, [_p, _p, _pdbl]),
+    "stc_score_main_topics": (_int, [_p, _p, _pi32, _pdbl, _pi64]),
+    "stc_score_members": (_int, [_p, _p, _pi64, _pi64]),
+    "stc_score_top_topics": (_int, [_p, _p, _i32, _pi32, _pdbl]),
+    "stc_score_top_documents": (_int, [_p, _p, _i64, _pi64, _pi64, _pdbl]),
+    "stc_lda_important_terms": (_int, [_p, _p, _p, _pi32, _i32, _i32, _i32, _pi32, _pdbl, _pi32]),
 }
 
 

@@ -91,6 +91,112 @@ def _counters(lib, h):
             "kernels": {f: int(kc[i]) for i, f in enumerate(KERNEL_FAMILIES)}}
 
 
+class DocumentScores:
+    """Owns one stc_dscore: a set of documents scored once, γ and its row sums kept on the GPU (include/stc.h,
+    "Document scores").  Made by ``LdaHandle.score`` / ``LDAModel.score`` or ``DocumentScores.from_gamma``; every
+    method is a device query, none copies γ to the host."""
+
+    def __init__(self, ctx: Context, handle, lda: "LdaHandle | None" = None):
+        self.ctx, self.handle, self._lda = ctx, handle, lda
+        rows, k, nonempty = C.c_int64(), C.c_int32(), C.c_int64()
+        L.check(ctx.lib.stc_score_shape(handle, C.byref(rows), C.byref(k), C.byref(nonempty)))
+        self.num_rows, self.k, self.nonempty = rows.value, k.value, nonempty.value
+
+    @staticmethod
+    def from_gamma(ctx: Context, gamma, empty=None) -> "DocumentScores":
+        """the scores of a host matrix (rows×k, finite and >= 0; ``empty[r]`` marks row r as an empty document): the
+        EM model's doc_topics, or planted values"""
+        g = L.as_f64(gamma)
+        if g.ndim != 2:
+            raise ValueError("gamma must be rows×k")
+        e = None if empty is None else np.ascontiguousarray(empty, dtype=np.uint8)
+        if e is not None and e.shape != (g.shape[0],):
+            raise ValueError("empty must have one entry per row")
+        h = C.c_void_p()
+        L.check(ctx.lib.stc_score_from_gamma(ctx.handle, L.ptr(g, C.c_double), L.ptr(e, C.c_uint8), g.shape[0],
+                                             g.shape[1], C.byref(h)))
+        return DocumentScores(ctx, h)
+
+    def topicDistribution(self):
+        """θ rows×k = γ / Σ_j γ_j, zeros for empty rows: bitwise ``LdaHandle.topic_distribution`` of the same call"""
+        out = np.zeros((self.num_rows, self.k), np.float64)
+        L.check(self.ctx.lib.stc_score_topic_distribution(self.ctx.handle, self.handle, L.ptr(out, C.c_double)))
+        return out
+
+    def mainTopics(self):
+        """(topic int32[rows], weight float64[rows], counts int64[k]): the topic with the largest θ — among equal
+        maxima the largest index, as LDALoader.scala:136 — and that θ; an empty row: −1 and 0"""
+        topic = np.zeros(self.num_rows, np.int32)
+        weight = np.zeros(self.num_rows, np.float64)
+        counts = np.zeros(self.k, np.int64)
+        L.check(self.ctx.lib.stc_score_main_topics(self.ctx.handle, self.handle, L.ptr(topic, C.c_int32),
+                                                   L.ptr(weight, C.c_double), L.ptr(counts, C.c_int64)))
+        return topic, weight, counts
+
+    def members(self):
+        """(indptr int64[k+1], rows int64[nonempty]): the non-empty rows grouped by main topic, ascending inside one"""
+        indptr = np.zeros(self.k + 1, np.int64)
+        rows = np.zeros(self.nonempty, np.int64)
+        L.check(self.ctx.lib.stc_score_members(self.ctx.handle, self.handle, L.ptr(indptr, C.c_int64),
+                                               L.ptr(rows, C.c_int64)))
+        return indptr, rows
+
+    def topTopics(self, n):
+        """(topics int32[rows×N], weights float64[rows×N]), N = min(n, k): ``EmHandle.top_topics``' contract"""
+        m = max(0, min(int(n), self.k))
+        idx = np.zeros((self.num_rows, m), np.int32)
+        w = np.zeros((self.num_rows, m), np.float64)
+        L.check(self.ctx.lib.stc_score_top_topics(self.ctx.handle, self.handle, int(n), L.ptr(idx, C.c_int32),
+                                                  L.ptr(w, C.c_double)))
+        return idx, w
+
+    def topDocuments(self, n):
+        """(rows int64[k×N], weights float64[k×N]), N = min(n, non-empty rows): ``EmHandle.top_documents``' contract"""
+        cap = max(0, min(int(n), self.num_rows))
+        rows = np.zeros((self.k, cap), np.int64)
+        w = np.zeros((self.k, cap), np.float64)
+        got = C.c_int64()
+        L.check(self.ctx.lib.stc_score_top_documents(self.ctx.handle, self.handle, int(n), C.byref(got),
+                                                     L.ptr(rows, C.c_int64), L.ptr(w, C.c_double)))
+        return rows[:, :got.value].copy(), w[:, :got.value].copy()
+
+    def importantTerms(self, dataset, docTerms=100, topicTerms=300, n=10, topics=None):
+        """(terms int32[rows×n] padded with −1, values float64[rows×n] padded with 0, counts int32[rows]): per row
+        of ``dataset`` — the matrix that was scored — the first n of its docTerms largest entries (value descending,
+        term ascending) whose term is among the topicTerms heaviest terms of the row's main topic (``topics``: of
+        that topic instead; −1 skips the row).  LDALoader.scala:154-163 with its 100 / 300 / 10."""
+        if self._lda is None:
+            raise ValueError("importantTerms needs the scores of an LDA model (LdaHandle.score)")
+        h = self._lda
+        d, own = _as_device(self.ctx, dataset, h.dtype)
+        try:
+            width = max(0, int(n))
+            idx = np.zeros((self.num_rows, width), np.int32)
+            val = np.zeros((self.num_rows, width), np.float64)
+            cnt = np.zeros(self.num_rows, np.int32)
+            t = None if topics is None else L.as_i32(topics)
+            if t is not None and t.shape != (self.num_rows,):
+                raise ValueError("topics must have one entry per row")
+            L.check(self.ctx.lib.stc_lda_important_terms(h.handle, d.handle, self.handle, L.ptr(t, C.c_int32),
+                                                         int(docTerms), int(topicTerms), int(n), L.ptr(idx, C.c_int32),
+                                                         L.ptr(val, C.c_double), L.ptr(cnt, C.c_int32)))
+            return idx, val, cnt
+        finally:
+            if own:
+                d.free()
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.stc_score_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class LdaHandle:
     """Owns one stc_lda (optimizer state + LocalLDAModel parameters on the GPU)."""
 
@@ -189,6 +295,14 @@ class LdaHandle:
                                                         int(gamma_seed) & 0xFFFFFFFFFFFFFFFF, int(doc_id_base),
                                                         L.ptr(g0, C.c_double), L.ptr(out, C.c_double)))
         return out
+
+    def score(self, docs: DeviceCsr, gamma_seed=0, doc_id_base=0, gamma0=None) -> DocumentScores:
+        """the E-step of ``topic_distribution`` with γ kept on the GPU (stc_lda_score)"""
+        g0 = None if gamma0 is None else L.as_f64(gamma0)
+        h = C.c_void_p()
+        L.check(self.ctx.lib.stc_lda_score(self.handle, docs.handle, int(gamma_seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(doc_id_base), L.ptr(g0, C.c_double), C.byref(h)))
+        return DocumentScores(self.ctx, h, self)
 
     def describe(self, max_terms=10):
         n = min(int(max_terms), self.vocab_size)
@@ -681,6 +795,42 @@ class LDAModel:
                 d.free()
 
     topicDistribution = transform
+
+    def score(self, dataset, gamma0=None) -> DocumentScores:
+        """``transform``'s E-step with the result kept on the GPU: main topics, members, ranked lists and important
+        terms are device queries of the returned ``DocumentScores``"""
+        d, own = _as_device(self._h.ctx, dataset, self._h.dtype)
+        try:
+            return self._h.score(d, self.gammaSeed, 0, gamma0)
+        finally:
+            if own:
+                d.free()
+
+    def report(self, dataset, vocabulary=None, docTerms=100, topicTerms=300, n=10, gamma0=None):
+        """LDALoader's report (LDALoader.scala:108-163, :171-199) as plain data, written nowhere:
+        ``{"documents": [{"row", "topicDistribution", "mainTopic", "mainTopicWeight", "importantTerms",
+        "importantTermValues"}], "topics": [{"topic", "count", "rows"}]}``.  importantTerms holds strings when a
+        vocabulary (term index → string) is given, else term indices; an empty row has mainTopic −1 and no terms."""
+        d, own = _as_device(self._h.ctx, dataset, self._h.dtype)
+        try:
+            s = self._h.score(d, self.gammaSeed, 0, gamma0)
+            try:
+                theta = s.topicDistribution()
+                topic, weight, counts = s.mainTopics()
+                indptr, rows = s.members()
+                idx, val, cnt = s.importantTerms(d, docTerms, topicTerms, n)
+            finally:
+                s.close()
+        finally:
+            if own:
+                d.free()
+        name = (lambda i: int(i)) if vocabulary is None else (lambda i: vocabulary[int(i)])
+        docs = [{"row": r, "topicDistribution": theta[r], "mainTopic": int(topic[r]), "mainTopicWeight": float(weight[r]),
+                 "importantTerms": [name(i) for i in idx[r, :cnt[r]]], "importantTermValues": val[r, :cnt[r]].copy()}
+                for r in range(theta.shape[0])]
+        topics = [{"topic": t, "count": int(counts[t]), "rows": rows[indptr[t]:indptr[t + 1]].copy()}
+                  for t in range(self.k)]
+        return {"documents": docs, "topics": topics}
 
     # ---- persistence: [U] LocalLDAModel.save / LocalLDAModel.load (SaveLoadV1_0 layout, stc.io)
     def save(self, path, overwrite=False):
