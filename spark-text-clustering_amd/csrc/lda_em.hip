@@ -28,7 +28,7 @@
 // else — counts, α, η, N_k, inv, γ, accumulators, partials, the scalars — is fp64 in the same order in both
 // instantiations.  N_k is the fp64 column sum of the stored N_wk.
 //
-// Ranked queries (describe, top_documents, top_topics): selections over the resident state by em_rank.hip's
+// Ranked queries (describe, top_documents, top_topics): selections over the resident state by rank.hip's
 // kernels; this file sizes their scratch, feeds them the state's buffers and copies the lists out.
 #include <hipcub/hipcub.hpp>
 
@@ -36,8 +36,9 @@
 #include <vector>
 
 #include "collectives.h"
-#include "em_rank.h"
 #include "lda_em.h"
+#include "rank.h"
+#include "rank_key.h"
 #include "stc_handles.h"
 
 namespace stc {
@@ -158,14 +159,7 @@ __global__ __launch_bounds__(256) void k_em_pass(const PassArgs<T> a) {
         best = up ? gi : best;
         bj = up ? j : bj;
       }
-#pragma unroll
-      for (int off = KP / 2; off > 0; off >>= 1) {  // the slot's lanes: larger value, then smaller index
-        const double ov = __shfl_xor(best, off, 64);
-        const int oj = __shfl_xor(bj, off, 64);
-        const bool take = (ov > best) | ((ov == best) & (oj < bj));
-        best = take ? ov : best;
-        bj = take ? oj : bj;
-      }
+      rank::row_argmax<false>(KP, best, bj);  // the slot's lanes: larger value, then smaller index
       if (valid && j0 == 0) a.assign[ed] = bj;
       continue;
     }
@@ -429,17 +423,10 @@ __global__ void k_em_chunk_fill(const int64_t* __restrict__ choff, int64_t n, in
   for (int64_t c = choff[v]; c < choff[v + 1]; ++c) chunk_vertex[c] = (int32_t)v;
 }
 
-inline unsigned blocks_for(int64_t n, int per = 256) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
 inline unsigned strided_blocks(int64_t n) { return (unsigned)std::min<int64_t>(std::max<int64_t>(1, ceil_div(n, 256)), 1 << 20); }
 
 void excl_scan(hipStream_t s, DevBuf& tmp, const int64_t* in, int64_t* out, int64_t n) {
   with_temp(tmp, [&](void* t, size_t& tb) { return hipcub::DeviceScan::ExclusiveSum(t, tb, in, out, (int)n, s); });
-}
-
-int pow2_at_least(int k) {
-  int p = 2;
-  while (p < k) p <<= 1;
-  return p;
 }
 
 template <typename T, int MODE>
@@ -495,7 +482,7 @@ struct stc_em {
   bool member = false;
   int64_t pos_base = 0;  // edges in the earlier shards
   DevBuf gdeg;           // int64[V]: every term's edges over all members (empty: the local graph is the whole one)
-  rank::Scratch rk;      // the ranked queries' scratch (em_rank.h; allocated by their first call)
+  rank::Scratch rk;      // the ranked queries' scratch (rank.h; allocated by their first call)
   int64_t doc_vertices = -1;  // the documents with an edge (counted by the first top_documents)
 };
 
@@ -882,7 +869,7 @@ void topic_assignments(stc_em& m, int64_t* indptr_out, int32_t* terms_out, int32
   wait_stream(*m.ctx, s);
 }
 
-// ---- ranked queries (em_rank.h) ----------------------------------------------------------------------
+// ---- ranked queries (rank.h) -------------------------------------------------------------------------
 bool is_f32(const stc_em& m) { return m.dtype == STC_F32; }
 
 // describeTopics: per topic the N = min(max_terms, V) largest N_wk[w][t], (count descending, term ascending),
@@ -893,17 +880,8 @@ void describe(stc_em& m, int32_t max_terms, int32_t* idx_out, double* weight_out
   STC_REQUIRE(max_terms > 0, "em: max_terms > 0");
   require_state(m);
   m.ctx->use();
-  hipStream_t s = m.ctx->stream;
-  const int64_t N = std::min<int64_t>(max_terms, m.V), total = N * m.k;
-  m.rk.out_row.reserve(8 * total);
-  m.rk.out_w.reserve(8 * total);
-  rank::select_columns(s, m.rk, m.nwk[m.cur].p, is_f32(m), m.V, m.k, N, nullptr, m.nk.as<double>(), 0,
-                       m.rk.out_row.as<int64_t>(), m.rk.out_w.as<double>());
-  std::vector<int64_t> rows((size_t)total);
-  HIP_CHECK(hipMemcpyAsync(rows.data(), m.rk.out_row.p, 8 * total, hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(weight_out, m.rk.out_w.p, 8 * total, hipMemcpyDeviceToHost, s));
-  wait_stream(*m.ctx, s);
-  std::copy(rows.begin(), rows.end(), idx_out);
+  rank::describe_columns(*m.ctx, m.rk, m.nwk[m.cur].p, is_f32(m), m.V, m.k, std::min<int64_t>(max_terms, m.V),
+                         m.nk.as<double>(), idx_out, weight_out);
 }
 
 // topDocumentsPerTopic over this handle's rows: N = min(max_docs, its document vertices) per topic, rows[t·N + i]

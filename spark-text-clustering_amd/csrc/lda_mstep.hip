@@ -459,23 +459,6 @@ void launch_topics_bound(hipStream_t s, const double* lam, const double* colsum,
   KERNEL_CHECK();
 }
 
-__global__ __launch_bounds__(256) void k_transpose_kv(const double* __restrict__ lam, int64_t V, int k,
-                                                      double* __restrict__ out, int32_t* __restrict__ idx) {
-  const int64_t total = V * k;
-  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
-    const int t = (int)(e / V);
-    const int64_t v = e - (int64_t)t * V;
-    out[e] = lam[v * k + t];
-    idx[e] = (int32_t)v;
-  }
-}
-
-void launch_transpose_kv(hipStream_t s, const double* lam, int64_t V, int k, double* out_kv,
-                         int32_t* idx_kv) {
-  k_transpose_kv<<<4096, 256, 0, s>>>(lam, V, k, out_kv, idx_kv);
-  KERNEL_CHECK();
-}
-
 __global__ void k_to_f32(const double* __restrict__ in, float* __restrict__ out, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     out[i] = (float)in[i];

@@ -2,8 +2,6 @@
 // every STC_* switch of a handle) and destroy, the model's setters and getters, and the readers — the E-step
 // alone, inference (topic distribution, the bound) and describe.  One submitMiniBatch per stc_lda_step /
 // stc_lda_next: lda_train.hip; the kernel chosen for a launch: lda_dispatch.hip; struct stc_lda: lda_handle.h.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -11,6 +9,7 @@
 
 #include "lda_handle.h"
 #include "lda_online.h"
+#include "rank.h"
 
 using namespace stc;
 using namespace stc::online;
@@ -467,40 +466,15 @@ int stc_lda_describe(stc_lda* L, int32_t max_terms, int32_t* idx_out, double* we
     STC_REQUIRE(L && idx_out && weight_out, "lda/idx_out/weight_out");
     STC_REQUIRE(max_terms > 0, "maxTermsPerTopic must be > 0");
     STC_REQUIRE(L->model.has_topics, "no topics yet");
+    // the API's documented limit by now, no kernel's: the selection takes any V < 2^31 with int64 offsets
     STC_REQUIRE(L->V * L->k < (int64_t(1) << 31), "describe: V*k must be < 2^31");
     L->ctx->use();
     gather_lambda(*L);
-    hipStream_t s = L->ctx->stream;
-    const int64_t n = L->V * L->k;
-    const int N = (int)std::min<int64_t>(max_terms, L->V);
-    DevBuf kv, kv_s, ix, ix_s, off, tmp;
-    kv.reserve(8 * n);
-    kv_s.reserve(8 * n);
-    ix.reserve(4 * n);
-    ix_s.reserve(4 * n);
-    off.reserve(8 * (L->k + 1));
-    std::vector<int64_t> ho((size_t)L->k + 1);
-    for (int t = 0; t <= L->k; ++t) ho[(size_t)t] = (int64_t)t * L->V;
-    HIP_CHECK(hipMemcpyAsync(off.p, ho.data(), 8 * (L->k + 1), hipMemcpyHostToDevice, s));
-    lda::launch_transpose_kv(s, L->model.lam.as<double>(), L->V, L->k, kv.as<double>(), ix.as<int32_t>());
-    // stable descending sort per topic ⇒ ties keep ascending term index (Scala's sortBy(-w))
-    with_temp(tmp, [&](void* t, size_t& tb) {
-      return hipcub::DeviceSegmentedRadixSort::SortPairsDescending(
-          t, tb, kv.as<double>(), kv_s.as<double>(), ix.as<int32_t>(), ix_s.as<int32_t>(), (int)n, L->k,
-          off.as<int64_t>(), off.as<int64_t>() + 1, 0, 64, s);
-    });
-    std::vector<double> cs((size_t)L->k);
-    HIP_CHECK(hipMemcpyAsync(cs.data(), L->model.colsum.p, 8 * L->k, hipMemcpyDeviceToHost, s));
-    std::vector<double> w((size_t)N);
-    for (int t = 0; t < L->k; ++t) {
-      HIP_CHECK(hipMemcpyAsync(idx_out + (int64_t)t * N, ix_s.as<int32_t>() + (int64_t)t * L->V, 4 * N,
-                               hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipMemcpyAsync(weight_out + (int64_t)t * N, kv_s.as<double>() + (int64_t)t * L->V, 8 * N,
-                               hipMemcpyDeviceToHost, s));
-    }
-    wait_stream(*L->ctx, s);
-    for (int t = 0; t < L->k; ++t)  // normalize(topic, 1.0): v / ‖v‖₁ (λ > 0)
-      for (int j = 0; j < N; ++j) weight_out[(int64_t)t * N + j] /= cs[(size_t)t];
+    // per topic the N heaviest λ[w][t], ties by ascending term (Scala's stable sortBy(-w)); the weight is
+    // normalize(topic, 1.0): λ[w][t] / colsum[t] (λ > 0)
+    rank::Scratch sc;
+    rank::describe_columns(*L->ctx, sc, L->model.lam.p, false, L->V, L->k, std::min<int64_t>(max_terms, L->V),
+                           L->model.colsum.as<double>(), idx_out, weight_out);
   });
 }
 

@@ -14,21 +14,22 @@
 //                  the position of that tile's first row of the topic.
 //   k_group_place  reads topic and those positions; a wave walks its tile 64 rows at a time in row order and
 //                  writes members[]: inside a topic the rows ascend, whatever the grid.
-// The two ranked lists call em_rank.h on (γ, rowsum).
+// The two ranked lists call rank.h on (γ, rowsum).
 //
-// Important terms: S_t as a k×V bit set (em_rank's column selection in raw mode over the resident λ, then
+// Important terms: S_t as a k×V bit set (rank.h's column selection in raw mode over the resident λ, then
 // k_terms_bits: integer atomicOr), and k_terms_select, one workgroup per document claimed by ticket:
-//   a row of at most kCap entries is loaded whole; a longer one gets a most-significant-digit radix selection over
-//   the 96-bit key (value bits made order-preserving, ~term), 8 bits a pass, which stops as soon as the keys at or
-//   above the selected prefix fit the candidate list (at the latest after 12 digits, when they are exactly the
-//   doc_terms first) and collects them; then a bitonic sort of the candidates by the key in LDS, the bit test of
-//   the first doc_terms against S_t and an ordered compaction (ballot prefix) of the first max_out.
+//   a row of at most kCap entries is loaded whole; a longer one gets rank_key.h's most-significant-digit radix
+//   selection over the 96-bit key (value key, ~term), 8 bits a pass, which stops as soon as the keys at or above
+//   the selected prefix fit the candidate list (at the latest after 12 digits, when they are exactly the
+//   doc_terms first) and collects them; then rank_key.h's bitonic sort of the candidates by the key in LDS, the
+//   bit test of the first doc_terms against S_t and an ordered compaction (ballot prefix) of the first max_out.
 // Ties at the threshold value are resolved by the key's term digits, so the result does not depend on the order
 // of a row's entries (stc_dcsr_upload does not require ascending indices), nor on the ticket order or the atomics:
 // counts are integers and the final order is a total order of the keys.
-#include "em_rank.h"
 #include "lda_handle.h"
 #include "lda_online.h"
+#include "rank.h"
+#include "rank_key.h"
 
 using namespace stc;
 
@@ -43,7 +44,7 @@ struct stc_dscore {
   // what the queries make on first use
   mutable bool grouped = false;
   mutable DevBuf indptr, members;  // int64[k+1], int64[nonempty]
-  mutable em::rank::Scratch rk;
+  mutable rank::Scratch rk;
 };
 
 namespace {
@@ -52,9 +53,6 @@ constexpr int kWidenCols = 16;  // topics of one LDS tile
 constexpr int kGroupTiles = 1024;  // at most this many tiles (waves) group the rows
 constexpr int kCap = 2048;         // candidates of one document sorted in LDS: 16 KiB of keys + 8 KiB of terms
 constexpr int kHistPitch = 257;    // a wave's 256 digit counters + 1
-constexpr int kDigits = 12;        // 8 of the value, 4 of the complemented term
-
-inline unsigned blocks_for(int64_t n, int64_t per) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
 
 // ---- widen + row sum -------------------------------------------------------------------------------------------
 // LDS: the tile holds `rows` segments of w <= 16 doubles at a pitch of w | 1 doubles.  Reading, lane i adds
@@ -118,13 +116,7 @@ __global__ __launch_bounds__(256) void k_score_main(const double* __restrict__ g
         if (x >= best) best = x, bj = j;
       }
     }
-    for (int off = lpr >> 1; off > 0; off >>= 1) {
-      const double ov = __shfl_xor(best, off, 64);
-      const int oj = __shfl_xor(bj, off, 64);
-      const bool take = (ov > best) | ((ov == best) & (oj > bj));
-      best = take ? ov : best;
-      bj = take ? oj : bj;
-    }
+    rank::row_argmax<true>(lpr, best, bj);
     if (valid && j0 == 0) {
       const bool none = s < 0.0 || bj < 0;  // bj < 0: a row of NaN only (unpinned)
       topic[r] = none ? -1 : bj;
@@ -214,41 +206,6 @@ __global__ void k_terms_bits(const int64_t* __restrict__ sel, int64_t n_per_topi
   atomicOr(&bits[t * W + (w >> 5)], 1u << (w & 31));
 }
 
-// a value's bits made to order like the value: −0 is read as 0, negatives below positives
-template <typename T>
-__device__ inline uint64_t value_key(T v) {
-  const double x = (double)v;
-  const uint64_t b = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ inline double key_value(uint64_t key) {
-  const uint64_t b = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-  return __longlong_as_double((long long)b);
-}
-__device__ inline uint32_t digit_of(uint64_t hi, uint32_t lo, int d) {
-  return d < 8 ? (uint32_t)(hi >> (56 - 8 * d)) & 255u : (lo >> (24 - 8 * (d - 8))) & 255u;
-}
-// the key's first nd digits against the prefix's: equal / at or above
-__device__ inline bool prefix_eq(uint64_t hi, uint32_t lo, uint64_t phi, uint32_t plo, int nd) {
-  if (nd == 0) return true;
-  if (nd <= 8) return ((hi ^ phi) >> (64 - 8 * nd)) == 0;
-  return hi == phi && ((lo ^ plo) >> (32 - 8 * (nd - 8))) == 0;  // nd <= 11 here
-}
-__device__ inline bool prefix_ge(uint64_t hi, uint32_t lo, uint64_t phi, uint32_t plo, int nd) {
-  if (nd == 0) return true;
-  if (nd <= 8) {
-    const int sh = 64 - 8 * nd;
-    return (hi >> sh) >= (phi >> sh);
-  }
-  if (nd == 12) return hi > phi || (hi == phi && lo >= plo);
-  const int sh = 32 - 8 * (nd - 8);
-  return hi > phi || (hi == phi && (lo >> sh) >= (plo >> sh));
-}
-// descending by (value key, ~term): the larger value first, then the smaller term
-__device__ inline bool key_before(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib) {
-  return ka > kb || (ka == kb && ia < ib);
-}
-
 // a block-uniform value read from LDS, as a scalar
 __device__ inline int64_t uniform64(unsigned long long v) {
   const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
@@ -259,15 +216,7 @@ __device__ inline int64_t uniform64(unsigned long long v) {
 //  s_hist: one histogram per wave at a pitch of 257 counters — wave w's digit d sits on bank (w + d) mod 32, so the
 //    four waves counting one digit (a row of near-equal values) do not queue on one bank; lanes of one wave that
 //    count the same digit are serialised by the atomic unit, which no layout avoids.
-//  s_key (u64) / s_idx (u32), the bitonic sort: thread p of a step holds the pair a = 2p − (p & (stride − 1)),
-//    b = a + stride.  Read in that order, lanes l and l + 16 of a 32-lane ds_read group would meet on one bank at
-//    every stride below 32 (a advances by 32 elements per 16 pairs: the a's of a 64-element window are its elements
-//    with the stride bit clear).  So lanes with bit 4 set read b first and a second: the first instruction then
-//    takes the window's first 32 elements with the stride bit clear from lanes 0–15 and its last 32 with the bit
-//    set from lanes 16–31 — all 32 residues mod 32, conflict-free for the u64 reads (banks (a/4) mod 64: 32
-//    doubles a row) and the u32 reads and writes (32 banks); at strides >= 32 both halves are contiguous runs.
-//    ds_write_b64 groups are 16 contiguous lanes on 16 double slots, so the key writes swap on lane bit 3 instead
-//    (the same argument on a 32-element window).
+//  s_key (u64) / s_idx (u32): the candidate list, in the layout rank_key.h's block_bitonic_sort argues.
 template <typename T>
 __global__ __launch_bounds__(256) void k_terms_select(const int64_t* __restrict__ indptr, const int32_t* __restrict__ indices,
                                                       const T* __restrict__ values, const int32_t* __restrict__ topic,
@@ -298,63 +247,39 @@ __global__ __launch_bounds__(256) void k_terms_select(const int64_t* __restrict_
       uint32_t m;  // candidates in s_key / s_idx
       if (n <= kCap) {
         for (int i = tid; i < (int)n; i += 256) {
-          s_key[i] = value_key(values[e0 + i]);
+          s_key[i] = rank::value_key(values[e0 + i]);
           s_idx[i] = (uint32_t)indices[e0 + i];
         }
         m = (uint32_t)n;
       } else {
-        uint64_t phi = 0;
-        uint32_t plo = 0, above = 0;
-        int nd = 0;
+        rank::Prefix pre = {0, 0, 0};
+        uint32_t above = 0;
         for (;;) {
           for (int i = tid; i < 4 * kHistPitch; i += 256) s_hist[i] = 0;
           __syncthreads();
           for (int64_t i = tid; i < n; i += 256) {
-            const uint64_t hi = value_key(values[e0 + i]);
+            const uint64_t hi = rank::value_key(values[e0 + i]);
             const uint32_t lo = ~(uint32_t)indices[e0 + i];
-            if (prefix_eq(hi, lo, phi, plo, nd)) atomicAdd(&s_hist[wave * kHistPitch + digit_of(hi, lo, nd)], 1u);
+            if (pre.matches(hi, lo)) atomicAdd(&s_hist[wave * kHistPitch + pre.digit(hi, lo)], 1u);
           }
           __syncthreads();
-          if (wave == 0) {  // lane l owns digits 255 − 4l … 252 − 4l; the digit that takes the count to DT
-            uint32_t c[4], tot = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int dg = 255 - 4 * lane - q;
-              c[q] = s_hist[dg] + s_hist[kHistPitch + dg] + s_hist[2 * kHistPitch + dg] + s_hist[3 * kHistPitch + dg];
-              tot += c[q];
-            }
-            uint32_t incl = tot;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-              const uint32_t o = __shfl_up(incl, off, 64);
-              if (lane >= off) incl += o;
-            }
-            uint32_t before = above + incl - tot;
-            const bool mine = before < (uint32_t)DT && before + tot >= (uint32_t)DT;
-            if (mine) {
-              int q = 0;
-              while (q < 3 && before + c[q] < (uint32_t)DT) before += c[q], ++q;
-              s_digit = 255 - 4 * lane - q;
-              s_above = before;
-              s_in_digit = c[q];
-            }
+          if (wave == 0) {  // the digit that takes the count to DT, over the four waves' histograms
+            const rank::DigitPick p = rank::pick_digit(s_hist, 4, kHistPitch, above, (uint32_t)DT);
+            if (lane == 0) s_digit = p.digit, s_above = p.above, s_in_digit = p.in_digit;
           }
           __syncthreads();
-          const uint32_t dg = s_digit;
-          if (nd < 8) phi |= (uint64_t)dg << (56 - 8 * nd);
-          else plo |= dg << (24 - 8 * (nd - 8));
+          pre.append(s_digit);
           above = s_above;
-          nd += 1;
-          const bool done = above + s_in_digit <= (uint32_t)kCap || nd == kDigits;
+          const bool done = pre.done(above + s_in_digit, (uint32_t)kCap);
           __syncthreads();
           if (done) break;  // block-uniform
         }
         if (tid == 0) s_cnt = 0;
         __syncthreads();
         for (int64_t i = tid; i < n; i += 256) {
-          const uint64_t hi = value_key(values[e0 + i]);
+          const uint64_t hi = rank::value_key(values[e0 + i]);
           const uint32_t ix = (uint32_t)indices[e0 + i];
-          if (!prefix_ge(hi, ~ix, phi, plo, nd)) continue;
+          if (!pre.at_or_above(hi, ~ix)) continue;
           const uint32_t p = atomicAdd(&s_cnt, 1u);
           if (p < (uint32_t)kCap) {  // always, unless a row repeats one (value, term) entry past the list
             s_key[p] = hi;
@@ -371,27 +296,7 @@ __global__ __launch_bounds__(256) void k_terms_select(const int64_t* __restrict_
         s_idx[i] = 0xFFFFFFFFu;
       }
       __syncthreads();
-      const bool r16 = (lane & 16) != 0, w8 = (lane & 8) != 0;
-      for (uint32_t size = 2; size <= P; size <<= 1) {
-        for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-          for (uint32_t p = tid; p < P / 2; p += 256) {
-            const uint32_t a = 2 * p - (p & (stride - 1)), b = a + stride;
-            const uint32_t x = r16 ? b : a, y = r16 ? a : b;
-            const uint64_t kx = s_key[x], ky = s_key[y];
-            const uint32_t ix = s_idx[x], iy = s_idx[y];
-            const uint64_t ka = r16 ? ky : kx, kb = r16 ? kx : ky;
-            const uint32_t ia = r16 ? iy : ix, ib = r16 ? ix : iy;
-            const bool first = (a & size) == 0;  // this run sorts in the contract's order, the next one reversed
-            if (key_before(kb, ib, ka, ia) == first) {
-              s_key[w8 ? b : a] = w8 ? ka : kb;
-              s_key[w8 ? a : b] = w8 ? kb : ka;
-              s_idx[x] = r16 ? ia : ib;
-              s_idx[y] = r16 ? ib : ia;
-            }
-          }
-          __syncthreads();
-        }
-      }
+      rank::block_bitonic_sort(s_key, s_idx, P);
       // the first L entries are L_d; those in S_t leave in order, max_out at most
       const int L = (int)min((uint32_t)DT, m);
       const uint32_t* trow = bits + (int64_t)t * W;
@@ -415,7 +320,7 @@ __global__ __launch_bounds__(256) void k_terms_select(const int64_t* __restrict_
         const int p = off + __popcll(bal & below);
         if (in && p < max_out) {
           idx_out[d * max_out + p] = (int32_t)w;
-          val_out[d * max_out + p] = key_value(s_key[i]);
+          val_out[d * max_out + p] = rank::key_value(s_key[i]);
         }
         found += total;
         __syncthreads();
@@ -449,12 +354,6 @@ const stc_dscore& checked(stc_ctx* ctx, const stc_dscore* score) {
   return *score;
 }
 
-int lanes_per_row(int k) {
-  int p = 2;
-  while (p < k && p < 64) p <<= 1;
-  return p;
-}
-
 // rowsum, the main topics and the counts from γ in `src` (T, or the score's own doubles when src == S.gamma.p)
 template <typename T>
 void finish(stc_dscore& S, const T* src, const int64_t* ptr, const uint8_t* empty) {
@@ -470,7 +369,7 @@ void finish(stc_dscore& S, const T* src, const int64_t* ptr, const uint8_t* empt
     k_score_widen<T><<<blocks_for(S.rows, 64), 64, 0, s>>>(src, ptr, empty, S.rows, S.k, S.gamma.as<double>(),
                                                            S.rowsum.as<double>());
     KERNEL_CHECK();
-    const int lpr = lanes_per_row(S.k);
+    const int lpr = std::min(pow2_at_least(S.k), 64);
     const int64_t waves = ceil_div(S.rows, 64 / lpr);
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(waves, 4), (int64_t)c.cus * 8);
     k_score_main<<<grid, 256, 0, s>>>(S.gamma.as<double>(), S.rowsum.as<double>(), S.rows, S.k, lpr, S.topic.as<int32_t>(),
@@ -636,7 +535,7 @@ int stc_score_top_topics(stc_ctx* ctx, const stc_dscore* score, int32_t n_topics
       const int64_t total = S.rows * N;
       S.rk.out_row.reserve(4 * total);
       S.rk.out_w.reserve(8 * total);
-      em::rank::select_rows(s, S.gamma.p, false, S.rowsum.as<double>(), S.rows, S.k, N, S.rk.out_row.as<int32_t>(),
+      rank::select_rows(s, S.gamma.p, false, S.rowsum.as<double>(), S.rows, S.k, N, S.rk.out_row.as<int32_t>(),
                             S.rk.out_w.as<double>());
       if (idx_out) HIP_CHECK(hipMemcpyAsync(idx_out, S.rk.out_row.p, 4 * total, hipMemcpyDeviceToHost, s));
       if (weight_out) HIP_CHECK(hipMemcpyAsync(weight_out, S.rk.out_w.p, 8 * total, hipMemcpyDeviceToHost, s));
@@ -655,7 +554,7 @@ int stc_score_top_documents(stc_ctx* ctx, const stc_dscore* score, int64_t max_d
     if (N > 0) {
       S.rk.out_row.reserve(8 * total);
       S.rk.out_w.reserve(8 * total);
-      em::rank::select_columns(s, S.rk, S.gamma.p, false, S.rows, S.k, N, S.rowsum.as<double>(), nullptr, 0,
+      rank::select_columns(s, S.rk, S.gamma.p, false, S.rows, S.k, N, S.rowsum.as<double>(), nullptr, 0,
                                S.rk.out_row.as<int64_t>(), S.rk.out_w.as<double>());
       for (int t = 0; t < S.k; ++t) {
         if (row_out)
@@ -700,7 +599,7 @@ int stc_lda_important_terms(stc_lda* L, const stc_dcsr* docs, const stc_dscore* 
     // S_t as bits: word (t, w >> 5), bit w & 31
     const int64_t W = ceil_div(L->V, 32), N = std::min<int64_t>(topic_terms, L->V);
     DevBuf bits, sel_row, sel_w, topics, ticket, d_idx, d_val, d_n;
-    em::rank::Scratch sc;
+    rank::Scratch sc;
     bits.reserve(4 * (size_t)W * k);
     if (N == L->V) {
       HIP_CHECK(hipMemsetAsync(bits.p, 0xFF, 4 * (size_t)W * k, s));
@@ -708,7 +607,7 @@ int stc_lda_important_terms(stc_lda* L, const stc_dcsr* docs, const stc_dscore* 
       HIP_CHECK(hipMemsetAsync(bits.p, 0, 4 * (size_t)W * k, s));
       sel_row.reserve(8 * (size_t)N * k);
       sel_w.reserve(8 * (size_t)N * k);
-      em::rank::select_columns(s, sc, L->model.lam.p, false, L->V, k, N, nullptr, nullptr, 0, sel_row.as<int64_t>(),
+      rank::select_columns(s, sc, L->model.lam.p, false, L->V, k, N, nullptr, nullptr, 0, sel_row.as<int64_t>(),
                                sel_w.as<double>());
       k_terms_bits<<<blocks_for(N * k, 256), 256, 0, s>>>(sel_row.as<int64_t>(), N, k, W, bits.as<uint32_t>());
       KERNEL_CHECK();

@@ -114,8 +114,6 @@ void launch_init_lambda(hipStream_t s, double* lam, int64_t V, int k, uint64_t s
 void launch_topics_bound(hipStream_t s, const double* lam, const double* colsum, int64_t V, int k,
                          double eta, double* partials, int64_t nblocks);
 void launch_to_f32(hipStream_t s, const double* in, float* out, int64_t n);
-void launch_transpose_kv(hipStream_t s, const double* lam, int64_t V, int k, double* out_kv,
-                         int32_t* idx_kv);
 
 }  // namespace lda
 }  // namespace stc

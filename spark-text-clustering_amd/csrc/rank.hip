@@ -1,22 +1,21 @@
-// em_rank.hip — ranked queries over the EM state (em_rank.h): selection instead of a sort.
+// rank.hip — ranked queries over a resident matrix (rank.h): selection instead of a sort.
 //
-// Column selection (describeTopics, topDocumentsPerTopic): per topic the N largest of R values, ordered by
-// (value descending, row ascending).  The values are non-negative doubles, so their bit patterns order like
-// the values (−0 is read as 0); every entry has the 96-bit key (value bits, ~row), all keys of a column are
-// distinct, and the contract's order is the keys' descending order.  A most-significant-digit radix selection
-// over that key, 8 bits per pass, 12 passes at most:
+// Column selection (describeTopics, topDocumentsPerTopic, the important terms' S_t): per topic the N largest of R
+// values, ordered by (value descending, row ascending).  Every entry has rank_key.h's 96-bit key (the value's
+// order-preserving bits, ~row); all keys of a column are distinct, and the contract's order is the keys' descending
+// order.  A most-significant-digit radix selection over that key, 8 bits per pass, 12 passes at most:
 //   k_rank_hist   a block reads a tile of kTileRows rows × up to kTopicGroup topics (row segments, coalesced),
 //                 counts the current digit of the entries that match the topic's selected prefix in LDS
 //                 (integer atomics) and adds its non-zero counters to the topic's global histogram.
-//   k_rank_scan   per topic: walks the histogram from digit 255 down to the digit that holds the N-th key,
-//                 appends it to the prefix and clears the histogram.  A topic is done once the keys at or
-//                 above its prefix number at most N + kSlack (they fit the candidate list), at the latest
-//                 after the last digit, when they number exactly N.  A block all of whose topics are done
-//                 returns before it reads anything.
+//   k_rank_scan   per topic: rank_key.h's digit pick finds the digit that holds the N-th key; it is appended to
+//                 the prefix and the histogram cleared.  A topic is done once the keys at or above its prefix
+//                 number at most N + kSlack (they fit the candidate list), at the latest after the last digit,
+//                 when they number exactly N.  A block all of whose topics are done returns before it reads
+//                 anything.
 //   k_rank_collect appends every key at or above the prefix to the topic's candidate list (an integer
 //                 counter; the list is unordered).
-//   k_rank_sort   one block per topic: a bitonic sort of the candidates by the key (in LDS up to kLdsSort
-//                 entries, else in the list itself), then the first N leave in the contract's order.
+//   k_rank_sort   one block per topic: rank_key.h's bitonic sort of the candidates by the key (in LDS up to
+//                 kLdsSort entries, else in the list itself), then the first N leave in the contract's order.
 // Counts are integers and the final order is a total order of distinct keys, so the result depends on the
 // matrix alone: not on the grid, the tile, timing or the order of the atomics.  A pass reads R·k·sizeof(T)
 // bytes (+ 8R in the row-normalised mode); nothing of the matrix is copied, scratch is k·(256 counters +
@@ -26,12 +25,15 @@
 // order, whatever k.
 //
 // Row selection (topTopicsPerDocument): the EM pass's lane layouts (lda_em.hip) — KP lanes per row and 64/KP
-// rows per wave for k <= 64, NS register slices of 64 topics above — and N rounds of kAssign's (value, index)
+// rows per wave for k <= 64, NS register slices of 64 topics above — and N rounds of rank_key.h's (value, index)
 // butterfly; the winner's owner retires it.
-#include "em_rank.h"
+#include "rank.h"
+
+#include "collectives.h"
+#include "rank_key.h"
+#include "stc_handles.h"
 
 namespace stc {
-namespace em {
 namespace rank {
 
 namespace {
@@ -39,49 +41,28 @@ namespace {
 constexpr int kTileRows = 512;    // rows of one block's tile
 constexpr int kTopicGroup = 32;   // topics of one block: 32 × 257 counters = 32.1 KiB of LDS
 constexpr int kHistStride = 257;  // a topic's 256 counters + 1: topic t's digit d sits on bank (t + d) mod 32
-constexpr int kDigits = 12;       // 8 of the value bits, 4 of the complemented row
 constexpr int kSlack = 512;       // candidates a topic may keep beyond N (ends the passes early)
 constexpr int kLdsSort = 2048;    // candidates sorted in LDS (24 KiB); more are sorted in global memory
 
 struct Sel {
-  uint64_t hi, lo;   // the selected prefix: nd digits from the top of (hi, lo), the rest 0
+  Prefix prefix;     // the digits selected so far
   uint32_t above;    // keys strictly above the prefix
-  uint32_t nd;       // digits selected so far
   uint32_t done;
   uint32_t count;    // k_rank_collect's append counter
 };
 
-__device__ inline uint32_t digit_of(uint64_t hi, uint64_t lo, uint32_t d) {
-  return d < 8 ? (uint32_t)(hi >> (56 - 8 * d)) & 255u : (uint32_t)(lo >> (56 - 8 * (d - 8))) & 255u;
-}
-// the key's first nd digits against the prefix's: equal / at or above
-__device__ inline bool prefix_eq(uint64_t hi, uint64_t lo, const Sel& s) {
-  if (s.nd == 0) return true;
-  if (s.nd <= 8) return ((hi ^ s.hi) >> (64 - 8 * s.nd)) == 0;
-  return hi == s.hi && ((lo ^ s.lo) >> (64 - 8 * (s.nd - 8))) == 0;
-}
-__device__ inline bool prefix_ge(uint64_t hi, uint64_t lo, const Sel& s) {
-  if (s.nd == 0) return true;
-  if (s.nd <= 8) {
-    const int sh = 64 - 8 * s.nd;
-    return (hi >> sh) >= (s.hi >> sh);
-  }
-  const int sh = 64 - 8 * (s.nd - 8);
-  return hi > s.hi || (hi == s.hi && (lo >> sh) >= (s.lo >> sh));
-}
-
 // entry (r, t)'s key; false: row r is no candidate
 template <typename T, bool NORM>
 __device__ inline bool make_key(const T* __restrict__ m, const double* __restrict__ rowsum, int64_t r, int t, int k,
-                                uint64_t& hi, uint64_t& lo) {
+                                uint64_t& hi, uint32_t& lo) {
   double x = (double)m[r * k + t];
   if (NORM) {
     const double s = rowsum[r];
     if (s < 0.0) return false;
     if (s > 0.0) x = x / s;
   }
-  hi = x == 0.0 ? 0ull : (uint64_t)__double_as_longlong(x);
-  lo = (uint64_t)(~(uint32_t)r) << 32;
+  hi = value_key(x);
+  lo = ~(uint32_t)r;
   return true;
 }
 
@@ -107,9 +88,10 @@ __global__ __launch_bounds__(256) void k_rank_hist(const T* __restrict__ m, cons
     const int rl = e / width, tl = e - rl * width;
     const Sel& s = s_sel[tl];
     if (s.done) continue;
-    uint64_t hi, lo;
+    uint64_t hi;
+    uint32_t lo;
     if (!make_key<T, NORM>(m, rowsum, r0 + rl, tg + tl, k, hi, lo)) continue;
-    if (prefix_eq(hi, lo, s)) atomicAdd(&h[tl * kHistStride + digit_of(hi, lo, s.nd)], 1u);
+    if (s.prefix.matches(hi, lo)) atomicAdd(&h[tl * kHistStride + s.prefix.digit(hi, lo)], 1u);
   }
   __syncthreads();
   for (int tl = 0; tl < width; ++tl) {
@@ -118,6 +100,7 @@ __global__ __launch_bounds__(256) void k_rank_hist(const T* __restrict__ m, cons
   }
 }
 
+// cap: the candidate list's capacity, N + kSlack
 __global__ __launch_bounds__(256) void k_rank_scan(Sel* __restrict__ sel, uint32_t* __restrict__ hist, uint32_t N,
                                                    uint32_t cap) {
   __shared__ uint32_t h[256];
@@ -126,20 +109,13 @@ __global__ __launch_bounds__(256) void k_rank_scan(Sel* __restrict__ sel, uint32
   h[threadIdx.x] = hist[(int64_t)t * 256 + threadIdx.x];
   hist[(int64_t)t * 256 + threadIdx.x] = 0;
   __syncthreads();
-  if (threadIdx.x != 0) return;
+  if (threadIdx.x >= 64) return;
   Sel s = sel[t];
-  uint32_t above = s.above, b = 255, c = 0;
-  for (;; --b) {  // the digit whose keys take the count to N; digit 0 if the counts fall short (they do not)
-    c = h[b];
-    if (above + c >= N || b == 0) break;
-    above += c;
-  }
-  if (s.nd < 8) s.hi |= (uint64_t)b << (56 - 8 * s.nd);
-  else s.lo |= (uint64_t)b << (56 - 8 * (s.nd - 8));
-  s.above = above;
-  s.nd += 1;
-  s.done = (above + c <= cap || s.nd == kDigits) ? 1u : 0u;
-  sel[t] = s;
+  const DigitPick p = pick_digit(h, 1, 0, s.above, N);  // digit 0 if the counts fall short (they do not)
+  s.prefix.append(p.digit);
+  s.above = p.above;
+  s.done = s.prefix.done(p.above + p.in_digit, cap) ? 1u : 0u;
+  if (threadIdx.x == 0) sel[t] = s;
 }
 
 template <typename T, bool NORM>
@@ -154,20 +130,16 @@ __global__ __launch_bounds__(256) void k_rank_collect(const T* __restrict__ m, c
   const int rows = (int)min((int64_t)kTileRows, R - r0);
   for (int e = threadIdx.x; e < rows * width; e += 256) {
     const int rl = e / width, tl = e - rl * width;
-    uint64_t hi, lo;
+    uint64_t hi;
+    uint32_t lo;
     if (!make_key<T, NORM>(m, rowsum, r0 + rl, tg + tl, k, hi, lo)) continue;
-    if (!prefix_ge(hi, lo, s_sel[tl])) continue;
+    if (!s_sel[tl].prefix.at_or_above(hi, lo)) continue;
     const uint32_t pos = atomicAdd(&sel[tg + tl].count, 1u);
     if (pos < P) {  // always: a done topic has at most N + kSlack <= P such keys
       cand_key[(int64_t)(tg + tl) * P + pos] = hi;
       cand_row[(int64_t)(tg + tl) * P + pos] = (uint32_t)(r0 + rl);
     }
   }
-}
-
-// descending by (value bits, ~row): the larger value first, then the smaller row
-__device__ inline bool key_before(uint64_t ka, uint32_t ra, uint64_t kb, uint32_t rb) {
-  return ka > kb || (ka == kb && ra < rb);
 }
 
 // P: a power of two >= the topic's candidates
@@ -182,34 +154,25 @@ __global__ __launch_bounds__(256) void k_rank_sort(const Sel* __restrict__ sel, 
   uint64_t* gk = cand_key + (int64_t)t * P;
   uint32_t* gr = cand_row + (int64_t)t * P;
   const bool in_lds = P <= (uint32_t)kLdsSort;  // block-uniform
-  uint64_t* key = in_lds ? s_key : gk;
-  uint32_t* row = in_lds ? s_row : gr;
-  for (uint32_t i = threadIdx.x; i < P; i += 256) {  // padding sorts behind every key (a row is below 2^31)
-    const bool real = i < n;
-    if (in_lds || !real) {
-      key[i] = real ? gk[i] : 0ull;
-      row[i] = real ? gr[i] : 0xFFFFFFFFu;
+  // padding sorts behind every key (a row is below 2^31)
+  if (in_lds) {
+    for (uint32_t i = threadIdx.x; i < P; i += 256) {
+      s_key[i] = i < n ? gk[i] : 0ull;
+      s_row[i] = i < n ? gr[i] : 0xFFFFFFFFu;
     }
-  }
-  __syncthreads();
-  for (uint32_t size = 2; size <= P; size <<= 1) {
-    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-      for (uint32_t i = threadIdx.x; i < P / 2; i += 256) {
-        const uint32_t a = 2 * i - (i & (stride - 1)), b = a + stride;
-        const uint64_t ka = key[a], kb = key[b];
-        const uint32_t ra = row[a], rb = row[b];
-        const bool first = (a & size) == 0;  // this run sorts in the contract's order, the next one reversed
-        if (key_before(kb, rb, ka, ra) == first) {
-          key[a] = kb, key[b] = ka;
-          row[a] = rb, row[b] = ra;
-        }
-      }
-      __syncthreads();
+    __syncthreads();
+    block_bitonic_sort(s_key, s_row, P);
+  } else {
+    for (uint32_t i = n + threadIdx.x; i < P; i += 256) {
+      gk[i] = 0ull;
+      gr[i] = 0xFFFFFFFFu;
     }
+    __syncthreads();
+    block_bitonic_sort(gk, gr, P);
   }
   for (uint32_t i = threadIdx.x; i < N; i += 256) {
-    const double v = __longlong_as_double((long long)key[i]);
-    out_row[(int64_t)t * N + i] = row0 + (int64_t)row[i];
+    const double v = key_value(in_lds ? s_key[i] : gk[i]);
+    out_row[(int64_t)t * N + i] = row0 + (int64_t)(in_lds ? s_row[i] : gr[i]);
     out_w[(int64_t)t * N + i] = nk ? v / nk[t] : v;
   }
 }
@@ -264,14 +227,7 @@ __global__ __launch_bounds__(256) void k_rank_rows(const T* __restrict__ m, cons
       best = up ? x[i] : best;
       bj = up ? j0 + 64 * i : bj;
     }
-#pragma unroll
-    for (int off = KP / 2; off > 0; off >>= 1) {  // the row's lanes: larger value, then smaller index
-      const double ov = __shfl_xor(best, off, 64);
-      const int oj = __shfl_xor(bj, off, 64);
-      const bool take = (ov > best) | ((ov == best) & (oj < bj));
-      best = take ? ov : best;
-      bj = take ? oj : bj;
-    }
+    row_argmax<false>(KP, best, bj);  // the row's lanes: larger value, then smaller index
 #pragma unroll
     for (int i = 0; i < NS; ++i)
       if (j0 + 64 * i == bj) x[i] = -1.0;
@@ -281,8 +237,6 @@ __global__ __launch_bounds__(256) void k_rank_rows(const T* __restrict__ m, cons
     }
   }
 }
-
-inline unsigned blocks_for(int64_t n, int per) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
 
 template <typename T, bool NORM>
 void select_columns_as(hipStream_t s, Scratch& sc, const T* m, int64_t R, int k, int64_t N, const double* rowsum,
@@ -310,12 +264,6 @@ void select_columns_as(hipStream_t s, Scratch& sc, const T* m, int64_t R, int k,
   k_rank_sort<<<(unsigned)k, 256, 0, s>>>(sel, P, sc.cand_key.as<uint64_t>(), sc.cand_row.as<uint32_t>(), (uint32_t)N, nk,
                                           row0, out_row, out_w);
   KERNEL_CHECK();
-}
-
-int pow2_at_least(int k) {
-  int p = 2;
-  while (p < k) p <<= 1;
-  return p;
 }
 
 template <typename T>
@@ -372,6 +320,20 @@ void select_columns(hipStream_t s, Scratch& sc, const void* m, bool f32, int64_t
   }
 }
 
+void describe_columns(Ctx& c, Scratch& sc, const void* m, bool f32, int64_t R, int k, int64_t N, const double* nk,
+                      int32_t* idx_out, double* weight_out) {
+  hipStream_t s = c.stream;
+  const int64_t total = N * k;
+  sc.out_row.reserve(8 * total);
+  sc.out_w.reserve(8 * total);
+  select_columns(s, sc, m, f32, R, k, N, nullptr, nk, 0, sc.out_row.as<int64_t>(), sc.out_w.as<double>());
+  std::vector<int64_t> rows((size_t)total);
+  HIP_CHECK(hipMemcpyAsync(rows.data(), sc.out_row.p, 8 * total, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(weight_out, sc.out_w.p, 8 * total, hipMemcpyDeviceToHost, s));
+  wait_stream(c, s);
+  std::copy(rows.begin(), rows.end(), idx_out);
+}
+
 void select_rows(hipStream_t s, const void* m, bool f32, const double* rowsum, int64_t R, int k, int N,
                  int32_t* out_idx, double* out_w) {
   if (R == 0) return;
@@ -381,5 +343,4 @@ void select_rows(hipStream_t s, const void* m, bool f32, const double* rowsum, i
 }
 
 }  // namespace rank
-}  // namespace em
 }  // namespace stc

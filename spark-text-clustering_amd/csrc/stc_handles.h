@@ -103,6 +103,15 @@ struct Pinned : NoCopy {  // N host words the device copies into; zero when made
   }
 };
 
+// Launch geometry.  blocks_for: a grid of blocks of `per` elements over n of them, one block at the least.
+// pow2_at_least: the power of two at or above k, 2 at the least — the lanes a row of k topics takes.
+inline unsigned blocks_for(int64_t n, int64_t per = 256) { return (unsigned)std::max<int64_t>(1, ceil_div(n, per)); }
+inline int pow2_at_least(int k) {
+  int p = 2;
+  while (p < k) p <<= 1;
+  return p;
+}
+
 // Environment switches.  env_int: an integer clamped to [lo, hi], dflt when unset.  env_flag: by the value's
 // first character — a switch that is on by default is off only at '0', one that is off by default is on only at '1'.
 inline int env_int(const char* name, int dflt, int lo, int hi) {

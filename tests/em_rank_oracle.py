@@ -1,4 +1,4 @@
-"""NumPy restatement of the EM model's ranked queries (include/stc.h, "EM LDA, ranked queries"; csrc/em_rank.hip).
+"""NumPy restatement of the EM model's ranked queries (include/stc.h, "EM LDA, ranked queries"; csrc/rank.hip).
 
 Order: (value descending, index ascending) — ``np.lexsort((index, -value))``.  Row sums are sequential in
 ascending j (``np.cumsum(x, axis=1)[:, -1]``), the device's documented order, so the normalised weights are

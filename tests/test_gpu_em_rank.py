@@ -1,5 +1,5 @@
 """GPU: the EM model's ranked queries (stc_em_describe / _top_documents / _top_topics, their group forms,
-csrc/em_rank.hip) against the NumPy restatement (tests/em_rank_oracle.py).
+csrc/rank.hip) against the NumPy restatement (tests/em_rank_oracle.py).
 
 The oracle is fed the handle's own state read back (so an fp32 handle is compared on the values it stores).
 Comparison rule (em_rank_oracle): describe and top topics rank stored numbers — exact indices, describe's weights
@@ -97,7 +97,7 @@ def test_every_lane_layout(ctx, k, dtype):
 
 @pytest.mark.parametrize("D,V,k", [(5000, 4000, 5), (700, 4000, 100)])
 def test_several_tiles_and_ties_across_them(ctx, D, V, k):
-    """A block's tile is 512 rows (em_rank.hip kTileRows): 5000 and 4000 rows are several tiles with a partial last
+    """A block's tile is 512 rows (rank.hip kTileRows): 5000 and 4000 rows are several tiles with a partial last
     one, 700 rows are two.  Rows 3, the middle and R−2 hold the same counts, raised so that they lead topic 0: a
     tie of three across the first, a middle and the last tile."""
     rng = np.random.default_rng(200 + k)

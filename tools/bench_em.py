@@ -23,7 +23,7 @@ against is one kernel of the iteration; its time comes from a kernel trace of th
 
 The ranked queries ("ranked" in the line; --no-ranked skips them): describe(10), describe(300), top_documents(10)
 and top_topics(1) from the state the timed iterations left, each warm (one untimed call) as the median of
---repeats calls that end in the copy to the host — on the device selection (csrc/em_rank.hip) and, in the same
+--repeats calls that end in the copy to the host — on the device selection (csrc/rank.hip) and, in the same
 run, the way the question was answered before it: toLocal().describeTopics (the upload into an online handle
 untimed, reported as to_local_ms) and a download of N_dk plus NumPy.  floor_bytes is one read of the matrix.
 
