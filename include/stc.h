@@ -37,6 +37,8 @@
  *                               ranked lists a report adds (topTopicsPerDocument / topDocumentsPerTopic)
  *   stc_lda_important_terms     "Book most important words" — LDALoader.scala:86-94 (the book's tokens by
  *                               count), :154-163 (the first 100 ∩ the main topic's 300 terms, the first 10)
+ *   stc_term_cooccurrence,      the number behind the reference's one quality check, a person reading each topic's
+ *   stc_coherence               top terms — LDALoader.scala:66-69, 177-187: UMass / NPMI topic coherence
  *   stc_lda_bound               [U] LocalLDAModel.logLikelihood / logPerplexity
  *   stc_em_*                    [U] EMLDAOptimizer, the reference's default optimizer ("em", Params.scala:9) —
  *                               LDAClustering.scala:41; stc_em_log_likelihood is
@@ -710,6 +712,40 @@ typedef struct stc_dscore stc_dscore;
   int stc_lda_important_terms(stc_lda* lda, const stc_dcsr* docs, const stc_dscore* score, const int32_t* topic_of,
                               int32_t doc_terms, int32_t topic_terms, int32_t max_out, int32_t* idx_out,
                               double* value_out, int32_t* n_out);
+
+/* ---- Topic coherence (UMass, Mimno et al. 2011; document-level NPMI) -----------------------------
+ * A number for what LDALoader.scala:66-69, 177-187 leaves to the reader's eye: do a topic's top terms occur in the
+ * same documents.  Both measures are functions of document co-occurrence counts of the top terms, so the device
+ * counts (one integer pass over a resident matrix) and the host does the arithmetic.
+ *   stc_term_cooccurrence  terms int32[k×n] on the host: terms[t·n + i] is the term in slot i of topic t's list, best
+ *                         first; −1 marks an unused slot (all its counts are 0); any other value outside
+ *                         0 … n_cols−1: STC_ERR_INVALID_ARG.  A term may sit in several lists and more than once in
+ *                         one list: every slot counts on its own.  A document contains term w iff its row has an
+ *                         entry with index w and value > 0 (stc_idf_fit's rule: explicit zeros, negatives and NaN do
+ *                         not count); a row that lists w twice contains it once; rows need not be sorted; the matrix
+ *                         may be STC_F32 or STC_F64.
+ *                         df_out int64[k×n]: the documents that contain slot i's term; codf_out int64[k×n×n]: the
+ *                         documents that contain both slots' terms (symmetric, codf[t][i][i] = df[t][i]);
+ *                         *n_docs_out = the matrix's rows, empty ones included (IDF's m).  1 <= n <= 64,
+ *                         1 <= k <= 4096, fewer than 2^32 rows.  Any output pointer may be NULL.
+ *   stc_coherence         host only: no context, callable without a GPU.  For topic t the pairs (m, l), 1 <= m < n,
+ *                         0 <= l < m, m ascending and l ascending inside m; a pair with df[t][m] <= 0 or
+ *                         df[t][l] <= 0 (an unused slot, a term the corpus does not hold) is skipped; pairs_out[t]
+ *                         = the pairs that were not; the pair values are added sequentially in that order in fp64.
+ *                         STC_COH_UMASS: pair value ln((codf[t][m][l] + eps) / df[t][l]), topic_out[t] = the sum
+ *                         (0 without pairs); eps > 0 (Mimno et al.: 1).  STC_COH_NPMI, D = n_docs, c = codf[t][m][l]:
+ *                         −1 when c = 0, 0 when c = D, else ln(c·D / (df[t][m]·df[t][l])) / −ln(c / D); topic_out[t] =
+ *                         the mean over the counted pairs (0 without any); eps is ignored.  topic_out double[k],
+ *                         pairs_out int32[k], either may be NULL.  STC_ERR_INVALID_ARG: df or codf NULL, an unknown
+ *                         measure, n_docs <= 0, k or n < 1, a negative count.
+ * The matrix belongs to its stc_ctx: a handle of another context returns STC_ERR_INVALID_ARG.  Single device: a
+ * context connected to other ranks returns STC_ERR_STATE.  The count waits for queued work.  Its results are exact
+ * and bitwise reproducible: integer adds only on the device, no floating-point arithmetic and no float atomics. */
+enum stc_coherence_measure { STC_COH_UMASS = 0, STC_COH_NPMI = 1 };
+  int stc_term_cooccurrence(stc_ctx* ctx, const stc_dcsr* docs, const int32_t* terms /* k×n, host */, int32_t k,
+                            int32_t n, int64_t* df_out /* k×n */, int64_t* codf_out /* k×n×n */, int64_t* n_docs_out);
+  int stc_coherence(const int64_t* df, const int64_t* codf, int32_t k, int32_t n, int64_t n_docs, int measure,
+                    double eps, double* topic_out /* k */, int32_t* pairs_out /* k */);
 
 #ifdef __cplusplus
 }

@@ -1564,3 +1564,42 @@ JNIEXPORT void JNICALL FN(ldaImportantTerms)(JNIEnv* env, jclass c, jlong lda, j
   UNPIN(Int, topic_of, t, JNI_ABORT);
   check(env, st);
 }
+
+/* ---- topic coherence (stc_term_cooccurrence, stc_coherence) -------------------------------------------- */
+/* returns the matrix's rows; terms k × n (−1: unused slot), df k × n and codf k × n × n nullable */
+JNIEXPORT jlong JNICALL FN(termCooccurrence)(JNIEnv* env, jclass c, jlong ctx, jlong dcsr, jintArray terms, jint k, jint n,
+                                             jlongArray df, jlongArray codf) {
+  int64_t n_docs = 0;
+  const int64_t kn = (k > 0 && n > 0) ? (int64_t)k * n : 0;
+  if (NEED(terms, kn, "termCooccurrence terms") || NEED(df, kn, "termCooccurrence df") ||
+      NEED(codf, kn * n, "termCooccurrence codf"))
+    return 0;
+  jint* t = PIN(jint, Int, terms);
+  jlong* d = PIN(jlong, Long, df);
+  jlong* co = PIN(jlong, Long, codf);
+  int st = stc_term_cooccurrence(CTX(ctx), CSR(dcsr), (const int32_t*)t, k, n, (int64_t*)d, (int64_t*)co, &n_docs);
+  UNPIN(Long, codf, co, 0);
+  UNPIN(Long, df, d, 0);
+  UNPIN(Int, terms, t, JNI_ABORT);
+  if (check(env, st)) return 0;
+  return (jlong)n_docs;
+}
+
+/* host arithmetic only (no context): topic[k] and pairs[k] nullable; measure 0 UMass (eps > 0), 1 NPMI */
+JNIEXPORT void JNICALL FN(coherence)(JNIEnv* env, jclass c, jlongArray df, jlongArray codf, jint k, jint n, jlong n_docs,
+                                     jint measure, jdouble eps, jdoubleArray topic, jintArray pairs) {
+  const int64_t kn = (k > 0 && n > 0) ? (int64_t)k * n : 0, kk = k > 0 ? k : 0;
+  if (NEED(df, kn, "coherence df") || NEED(codf, kn * n, "coherence codf") || NEED(topic, kk, "coherence topic") ||
+      NEED(pairs, kk, "coherence pairs"))
+    return;
+  jlong* d = PIN(jlong, Long, df);
+  jlong* co = PIN(jlong, Long, codf);
+  jdouble* o = PIN(jdouble, Double, topic);
+  jint* p = PIN(jint, Int, pairs);
+  int st = stc_coherence((const int64_t*)d, (const int64_t*)co, k, n, n_docs, measure, eps, o, (int32_t*)p);
+  UNPIN(Int, pairs, p, 0);
+  UNPIN(Double, topic, o, 0);
+  UNPIN(Long, codf, co, JNI_ABORT);
+  UNPIN(Long, df, d, JNI_ABORT);
+  check(env, st);
+}

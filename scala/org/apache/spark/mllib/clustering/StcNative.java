@@ -290,4 +290,14 @@ public final class StcNative {
    *  (unused slots −1 / 0), nOut[rows].  LDALoader's numbers: 100, 300, 10 */
   public static native void ldaImportantTerms(long lda, long dcsr, long score, int[] topicOf, int docTerms,
                                               int topicTerms, int maxOut, int[] idx, double[] value, int[] nOut);
+
+  // ---- topic coherence (stc_term_cooccurrence / stc_coherence: the number behind LDALoader.scala:66-69, 177-187)
+  /** document co-occurrence counts of k term lists of n slots (terms k × n, best first, −1 = unused) over a resident
+   *  matrix: df[k × n], codf[k × n × n] (nullable); a document contains a term iff its row has an entry of it with
+   *  value > 0.  Exact.  n <= 64, k <= 4096.  Returns the matrix's rows (IDF's m) */
+  public static native long termCooccurrence(long ctx, long dcsr, int[] terms, int k, int n, long[] df, long[] codf);
+  /** host only: per topic the UMass sum (measure 0, eps > 0) or the NPMI mean (measure 1) over the pairs whose two
+   *  terms occur in the corpus; topic[k], pairs[k] (nullable) */
+  public static native void coherence(long[] df, long[] codf, int k, int n, long nDocs, int measure, double eps,
+                                      double[] topic, int[] pairs);
 }

@@ -10,6 +10,7 @@ from . import io
 from .clustering import (LDA, ML_LDA_DEFAULT_SEED, DistributedLDAModel, DocumentScores, EmGroup, EmHandle, EMLDAOptimizer, LdaGroup,
                          LdaHandle, LDAModel, MllibLDA, OnlineLDAOptimizer, em_concentrations,
                          reference_mini_batch_fraction)
+from .coherence import coherence, term_cooccurrence
 from .core import Context, CsrMatrix, DeviceCsr
 from .count_vectorizer import CountVectorizer, CountVectorizerModel
 from .feature import IDF, DeviceTokens, HashingTF, IDFModel, Tokenizer, encode_texts, encode_tokens
@@ -21,5 +22,5 @@ __all__ = [
     "LDAModel", "DistributedLDAModel", "DocumentScores", "LdaGroup", "LdaHandle", "EmHandle", "EmGroup", "io", "MllibLDA", "OnlineLDAOptimizer",
     "EMLDAOptimizer", "em_concentrations", "ML_LDA_DEFAULT_SEED", "reference_mini_batch_fraction", "StcError", "StcIllegalArgument", "load", "STC_F32", "STC_F64", "STC_MIXED",
     "STC_HASH_STANDARD", "STC_HASH_SPARK24", "STC_LAYOUT_VK", "STC_LAYOUT_KV", "STC_ERR_INVALID_ARG", "STC_ERR_HIP",
-    "STC_ERR_RCCL", "STC_ERR_OOM", "STC_ERR_STATE",
+    "STC_ERR_RCCL", "STC_ERR_OOM", "STC_ERR_STATE", "coherence", "term_cooccurrence",
 ]

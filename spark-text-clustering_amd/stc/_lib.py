@@ -207,6 +207,8 @@ SIGNATURES = {
     "stc_score_top_topics": (_int, [_p, _p, _i32, _pi32, _pdbl]),
     "stc_score_top_documents": (_int, [_p, _p, _i64, _pi64, _pi64, _pdbl]),
     "stc_lda_important_terms": (_int, [_p, _p, _p, _pi32, _i32, _i32, _i32, _pi32, _pdbl, _pi32]),
+    "stc_term_cooccurrence": (_int, [_p, _p, _pi32, _i32, _i32, _pi64, _pi64, _pi64]),
+    "stc_coherence": (_int, [_pi64, _pi64, _i32, _i32, _i64, _int, _dbl, _pdbl, _pi32]),
 }
 
 

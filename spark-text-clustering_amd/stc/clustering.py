@@ -26,6 +26,7 @@ import math
 import numpy as np
 
 from . import _lib as L
+from .coherence import check_top_n, topic_coherence
 from .core import Context, CsrMatrix, DeviceCsr
 
 
@@ -832,6 +833,12 @@ class LDAModel:
                   for t in range(self.k)]
         return {"documents": docs, "topics": topics}
 
+    def topicCoherence(self, dataset, topN=10, measure="umass", eps=1.0):
+        """float64[k]: the UMass ("umass") or document-level NPMI ("npmi") coherence of each topic's ``topN`` terms
+        (``describeTopics``' lists) over ``dataset``, counted on the GPU (``stc.term_cooccurrence``)"""
+        topN = check_top_n(topN)
+        return topic_coherence(self.describeTopics(topN), dataset, measure, eps, self._h.ctx)
+
     # ---- persistence: [U] LocalLDAModel.save / LocalLDAModel.load (SaveLoadV1_0 layout, stc.io)
     def save(self, path, overwrite=False):
         """Write this model as a Spark mllib LocalLDAModel directory (stock Spark can load it)."""
@@ -887,6 +894,18 @@ class DistributedLDAModel:
             "alpha": np.full(em.k, alpha), "eta": eta, "gamma_shape": float(gamma_shape),
             "iteration_times": np.asarray(iteration_times, np.float64), "k": em.k, "vocab_size": em.vocab_size}, em=em)
 
+    def _edge_rows(self) -> CsrMatrix:
+        """the stored edges as rows, one per document vertex in ``doc_ids``' order (the training corpus)"""
+        d = self._d
+        src, term, cnt = d["edges"]
+        row = np.searchsorted(d["doc_ids"], src)
+        if row.size and (row.max() >= d["doc_ids"].size or np.any(d["doc_ids"][row] != src)):
+            raise ValueError("an edge names a document that has no vertex")
+        order = np.argsort(row, kind="stable")
+        indptr = np.zeros(d["doc_ids"].size + 1, np.int64)
+        np.cumsum(np.bincount(row, minlength=d["doc_ids"].size), out=indptr[1:])
+        return CsrMatrix(indptr, term[order], cnt[order], self.vocabSize)
+
     def _em_handle(self, ctx: Context | None = None) -> "EmHandle | EmGroup":
         """the GPU graph of this model: the trainer's, or one built from the stored edges and state"""
         if self._em is None:
@@ -894,15 +913,9 @@ class DistributedLDAModel:
             alpha = np.asarray(d["alpha"], np.float64)
             if np.any(alpha != alpha[0]):
                 raise ValueError("an EM model has a symmetric docConcentration")
-            src, term, cnt = d["edges"]
-            row = np.searchsorted(d["doc_ids"], src)
-            if row.size and (row.max() >= d["doc_ids"].size or np.any(d["doc_ids"][row] != src)):
-                raise ValueError("an edge names a document that has no vertex")
-            order = np.argsort(row, kind="stable")
-            indptr = np.zeros(d["doc_ids"].size + 1, np.int64)
-            np.cumsum(np.bincount(row, minlength=d["doc_ids"].size), out=indptr[1:])
+            rows = self._edge_rows()
             ctx = ctx or Context.get()
-            dev = DeviceCsr.upload(ctx, CsrMatrix(indptr, term[order], cnt[order], self.vocabSize), L.STC_F64)
+            dev = DeviceCsr.upload(ctx, rows, L.STC_F64)
             try:
                 em = EmHandle(ctx, dev, self.k, float(alpha[0]), float(d["eta"]))
             finally:
@@ -1004,6 +1017,13 @@ class DistributedLDAModel:
             idx, w = self._em_handle(ctx).describe(maxTermsPerTopic)
             return [(t, idx[t].astype(np.int64), w[t]) for t in range(self.k)]
         return self.toLocal(ctx=ctx).describeTopics(maxTermsPerTopic)
+
+    def topicCoherence(self, dataset=None, topN=10, measure="umass", eps=1.0, ctx: Context | None = None):
+        """float64[k]: ``LDAModel.topicCoherence`` for the terms of ``describeTopics(topN, device=True)``;
+        ``dataset=None`` counts over the model's own stored edges, the corpus it was trained on"""
+        topN = check_top_n(topN)
+        described = self.describeTopics(topN, ctx=ctx, device=True)
+        return topic_coherence(described, self._edge_rows() if dataset is None else dataset, measure, eps, ctx)
 
 
 class LDA:
